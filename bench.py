@@ -1,6 +1,8 @@
 """bench.py -- HR images/sec of the full G+D step (SRModel.optimize_parameters), ESRGAN x4 128->512.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line; the roofline, variant and CPU legs listed
+below run only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (dump_outputs()).
 N > 1: one rank per GPU, RCCL gradient all-reduce.  Under `torch.distributed.run` (RANK / WORLD_SIZE set) each
 process is one rank; a plain `python bench.py --gpus N` re-launches itself under torch.distributed.run on 127.0.0.1.
 `--dry-run-cpu` exercises the same launch + data-parallel host logic on CPU (gloo, the test suite's torch stand-in
@@ -12,7 +14,7 @@ split-operand form (`--mma bf16x3`: every fp32 operand split exactly into three 
 the bf16 matrix core, fp32 accumulate; error against fp64 comparable to the fp32 matrix-core instruction's: test bound 1.5 x + 2e-7 scale), with the same step on
 v_mfma_f32_32x32x2_f32 measured in the same process as `variant_f32_mfma`.
 Synthetic HR in [0,1), LR = avg_pool(HR, 4), resident in HBM before the timed region; random-init
-(kaiming x0.1) G/D and seeded VGG weights (no network access).  One JSON line on rank 0, with
+(kaiming x0.1) G/D and seeded VGG weights (no network access).  One JSON line on rank 0, with (`--full` only: null or absent otherwise)
   roofline     : the dominant kernel family (3x3 implicit-GEMM, forward + data-gradient launches),
                  algorithmic FLOP of every launch / HIP-event time of that launch, both summed over a
                  separate instrumented pass of the same steps (events on the launch stream);
@@ -20,7 +22,8 @@ Synthetic HR in [0,1), LR = avg_pool(HR, 4), resident in HBM before the timed re
                  1 warm-up + 3 timed steps, same shapes; N=1 runs only);
   cpu_reference: the reference's OWN SRModel timed by the same protocol in the build container (profiles/*_cpu_reference.json,
                  oracle/time_reference.py) -- the GPU box has no /root/reference.
-The GPU result is also written to stderr as `BENCH_GPU_LINE {...}` before the CPU leg starts, so a timeout in the
+  variant_*    : the other fp32 arithmetic, `use_amp`, the input pipeline in the loop, BASELINE configs[3] and [4] (1 GPU).
+With `--full` the GPU result is also written to stderr as `BENCH_GPU_LINE {...}` before the CPU leg starts, so a timeout in the
 CPU leg cannot lose it; stdout carries exactly one JSON line.
 """
 import argparse
@@ -167,6 +170,38 @@ def synthetic(batch, crop, seed, device):
     return lr.to(device), hr.to(device)
 
 
+DUMP_SR_MAX = 3 * 512 * 512 * BATCH_PER_GPU    # the default step's whole SR batch (48 MiB of float32); larger outputs are sampled
+DUMP_PARAM_SAMPLE = 1 << 18                    # parameters per network after the step (1 MiB of float32 each)
+
+
+def _seeded_sample(flat, k, seed):
+    """`flat` itself when it has <= k elements, else k of its elements at fixed, seeded, sorted positions."""
+    if flat.numel() <= k:
+        return flat
+    idx = torch.randint(0, flat.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(outdir, model, log):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as .npy files in `outdir` (< 64 MB in all):
+    sr.npy           the generated SR batch (SRModel.fake_H, float32; a seeded sample of DUMP_SR_MAX elements if larger)
+    loss_<name>.npy  every entry of get_current_log() (float64)
+    net{G,D}_params_sample.npy  a seeded sample of each trained network's parameters after the step's optimiser update (float32)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    sr = model.fake_H.detach().float()
+    sr = sr if sr.numel() <= DUMP_SR_MAX else _seeded_sample(sr.reshape(-1), DUMP_SR_MAX, 11)
+    np.save(os.path.join(outdir, "sr.npy"), sr.cpu().numpy().astype(np.float32))
+    for k, v in sorted(log.items()):
+        np.save(os.path.join(outdir, "loss_%s.npy" % k), np.array([v], dtype=np.float64))
+    for name, seed in (("netG", 12), ("netD", 13)):
+        net = getattr(model, name, None)
+        if net is None:
+            continue
+        flat = torch.cat([v.detach().float().reshape(-1) for v in net.state_dict().values() if torch.is_tensor(v) and v.is_floating_point()])
+        np.save(os.path.join(outdir, "%s_params_sample.npy" % name), _seeded_sample(flat, DUMP_PARAM_SAMPLE, seed).cpu().numpy().astype(np.float32))
+
+
 def cpu_reference_record():
     """The reference's own SRModel timed on CPU (N = 2, 1 warm-up + >= 3 steps) in the build container: newest
     committed profiles/*_cpu_reference.json, or None."""
@@ -191,7 +226,9 @@ def cpu_baseline(crop, steps=3, batch=2):
     batch 2 (reported per image), 1 warm-up + >= 3 timed steps."""
     from oracle import detrand, sr_oracle as O
     from trainner_amd.models.modules.architectures import RRDBNet_arch, discriminators
-    cores = min(os.cpu_count() or 1, 64)       # more threads than this only slow torch's CPU convs down
+    # the cores this process may use (affinity, OMP_NUM_THREADS when set), at most 64: more threads only slow torch's CPU convs down
+    avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    cores = min(avail, int(os.environ.get("OMP_NUM_THREADS") or avail), 64)
     torch.set_num_threads(cores)
     g = {k: v.detach().clone() for k, v in RRDBNet_arch.RRDBNet(3, 3, 64, 23).state_dict().items()}
     d = {k: v.detach().clone() for k, v in discriminators.Discriminator_VGG(crop, 3, 64).state_dict().items()}
@@ -441,6 +478,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="per-GPU batch (BASELINE configs[1]: 16)")
     ap.add_argument("--crop", type=int, default=CROP)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline pass, the other fp32 arithmetic, the 1-GPU "
+                         "variants (amp, input pipeline, configs 4 and 5) and the CPU baseline (each still switchable off below)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (SR batch, losses, parameter samples) as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--detail", action="store_true", help="per-shape kernel table on stderr")
@@ -560,9 +602,11 @@ def main():
     log = model.get_current_log()
     if ops.chain_error_flag():
         raise SystemExit("bench: a conv_chain dependency wait timed out -- results are invalid")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, log)
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # separate instrumented pass: HIP events around every implicit-GEMM launch, on the launch stream
         # (with the input pipeline in the loop: on the last batch it delivered -- the kernels and shapes are the same)
         if feeder is not None:
@@ -643,7 +687,7 @@ def main():
     # second measurement in the same process: the same step in the OTHER fp32 arithmetic (headline bf16x3 -> v_mfma_f32_32x32x2_f32 and
     # vice versa).  (1 GPU only: the N > 1 runs are the scaling measurement and carry nothing extra.)
     variant, variant_key = None, None
-    if world == 1 and not args.amp and not args.no_variant and not args.no_roofline and feeder is None and not dry:
+    if args.full and world == 1 and not args.amp and not args.no_variant and not args.no_roofline and feeder is None and not dry:
         other = "f32" if args.mma == "bf16x3" else "bf16x3"
         code = {"f32": hip.MMA_F32, "bf16x3": hip.MMA_BF16X3}
         ops.MMA = ops.FP32_MMA = code[other]
@@ -672,7 +716,7 @@ def main():
     # (2 warm-up + `steps` timed steps + 1 instrumented step for its dominant kernel family): `use_amp`, the input pipeline in the loop,
     # and BASELINE configs[3] on one GPU (U-Net discriminator + LR synthesised by the GPU degradation pipeline)
     extra = {}
-    if world == 1 and not args.amp and not args.no_variant and not args.no_roofline and feeder is None and not dry \
+    if args.full and world == 1 and not args.amp and not args.no_variant and not args.no_roofline and feeder is None and not dry \
             and args.netd == "discriminator_vgg" and args.mma == "bf16x3":
         extra = driver_visible_variants(args, model, data, device, rank, barrier, step)
 
@@ -725,7 +769,7 @@ def main():
             out["invalid"] = "dry run"
         if shared_gpu:
             out["invalid"] = "ranks share one GPU (TNR_DP_DEVICE): the driver's N > 1 command on real kernels, not a scaling measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             print("BENCH_GPU_LINE " + json.dumps(out), file=sys.stderr, flush=True)    # safe before the CPU leg
             out["cpu_baseline"] = cpu_baseline(args.crop)
             out["cpu_reference"] = cpu_reference_record()

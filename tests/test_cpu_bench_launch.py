@@ -62,3 +62,36 @@ def test_bench_under_the_drivers_eight_rank_launch():
     assert j["value"] is None and j["invalid"] == "dry run"
     assert all(v == v for v in j["losses"].values())
     check_first_multi_gpu_run_keys(j, 8)
+
+
+def test_bench_dump_outputs_plain_run(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (CPU dry run): a plain run times exactly K steps, carries none of the
+    `--full` legs, and writes what the last timed step computed as float32 / float64 .npy files (< 64 MB) -- the same arrays on every run,
+    because the inputs and weights are seeded."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                              "--dry-run-cpu", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 2 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["n_gpus"] == 1
+        for k in ("roofline", "variant_f32_mfma", "variant_amp", "variant_feed_paired", "variant_config4", "variant_config5"):
+            assert j[k] is None, k
+        assert "cpu_baseline" not in j and "cpu_reference" not in j
+        files = sorted(os.listdir(d))
+        assert "sr.npy" in files and "netG_params_sample.npy" in files and "netD_params_sample.npy" in files, files
+        assert {"loss_%s.npy" % k for k in j["losses"]} <= set(files), files
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 * 10 ** 6
+        assert arrs["sr.npy"].shape == (2, 3, 64, 64) and np.isfinite(arrs["sr.npy"]).all()
+        for k, v in j["losses"].items():
+            assert abs(float(arrs["loss_%s.npy" % k][0]) - v) <= 1e-6 * max(1.0, abs(v)), k
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -3,7 +3,7 @@
 #   suite <tag> [pytest args]        the -m gpu suite (both arithmetic modes, tests/conftest.py) + smoke
 #   prof  <tag> <bf16x3|f32> [bench args]   rocprofv3 kernel stats of 3 bench steps + separate PMC passes (HBM traffic, MFMA busy) of 1
 #   prof_i2i <tag> <pix2pix|cyclegan> <resnet|unet>   the PMC passes of one step of tools/bench_i2i.py
-#   final <tag>                      suite + default bench line (with cpu_baseline) + prof bf16x3: the validation of a tree
+#   final <tag>                      suite + the `--full` bench line (with cpu_baseline) + prof bf16x3: the validation of a tree
 #   power <tag> <name> <cmd...>      the command with rocm-smi sampled every 0.5 s next to it (clock, socket power, temperature)
 #   run   <tag> <name> <cmd...>      any command, output to gpurun_out/<tag>_<name>.txt (tail printed)
 #   ab    <tag> <name> <v1,v2,..> <cmd...>  the command once per kernel-build variant (tools/build_variant.py; "" = the shipped library)
@@ -64,7 +64,7 @@ case $CMD in
   prof_i2i) prof_i2i "$@" ;;
   final)
     suite
-    ( time timeout 900 python bench.py ) > $O/${TAG}_bench_default.json.log 2> $O/${TAG}_bench_default.err
+    ( time timeout 900 python bench.py --full ) > $O/${TAG}_bench_default.json.log 2> $O/${TAG}_bench_default.err
     tail -1 $O/${TAG}_bench_default.json.log | cut -c1-1500
     prof bf16x3 > $O/${TAG}_prof_summary.txt 2>&1
     tail -4 $O/${TAG}_prof_summary.txt | cut -c1-600 ;;

@@ -4,7 +4,7 @@ TAG=${1:-rXX}; R=/root/repo; O=$R/gpurun_out; mkdir -p $O; cd $R
 {
 for A in "" "--feed paired" "--netd unet" "--netd unet --feed resrgan" "--amp"; do
   echo "== bench.py $A"
-  timeout 600 python bench.py $A --no-cpu-baseline --no-variant 2>/dev/null | tail -1 | python -c "
+  timeout 600 python bench.py $A --full --no-cpu-baseline --no-variant 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}
 print(d['value'], d['unit'], d['ms_per_step'], 'ms/step', d['dtype'], 'step_tflops', d.get('step_tflops'), '| dominant:', (r.get('kernel') or '')[:40], r.get('achieved'), r.get('unit'), 'frac', r.get('frac'), 'avg_launch_us', r.get('avg_launch_us'))
