@@ -402,6 +402,28 @@ int tnr_tensor2np_u8(const float *src, int32_t N, int32_t C, int32_t H, int32_t 
 int64_t tnr_metrics_workspace_bytes(int32_t N);
 int tnr_psnr_ssim_u8(const uint8_t *a, const uint8_t *b, int32_t N, int32_t H, int32_t W, int32_t C, int32_t crop,
                      int32_t want_ssim, double *out, double *ws, int64_t ws_bytes, void *stream);
+/* LPIPS validation metric, net-lin / squeeze / v0.1 / spatial = False (utils/metrics.py:37,232-280 ->
+ * models/modules/LPIPS/networks_basic.py:32-120).  The Fire convolutions of the SqueezeNet 1.1 backbone are tnr_conv_forward launches.
+ * tnr_lpips_stem: ScalingLayer + features[0] (conv 3x3 stride 2 no padding, 3 -> 64, bias) + ReLU of the image pairs (a[n], b[n]):
+ *   y = relu1 of the 2N images [a[0..N-1], b[0..N-1]], NHWC [2N, Ho, Wo, 64] (tnr_lpips_stem_dims).  src_kind 0: uint8 NHWC
+ *   [N, H, W, 3] (x = u8 / 127.5 - 1, divided in fp64, rounded to fp32), cropped by `crop` pixels per side; src_kind 1: fp32
+ *   NCHW [N, 3, H, W] in [-1, 1] (x = 2 x - 1 first if normalize).  shift / scale: the ScalingLayer buffers (3 floats each);
+ *   w: the OIHW [64, 3, 3, 3] weight, bias [64].
+ * tnr_maxpool3s2_ceil_fwd: nn.MaxPool2d(3, stride 2, ceil_mode = True), output size per tnr_maxpool3s2_ceil_dims; C % 4 == 0.
+ * tnr_lpips_head: per image n, the fixed-order fp64 sum over pixels of sum_c w[c] (f0[c] / (|f0| + 1e-10) - f1[c] / (|f1| + 1e-10))^2,
+ *   f0 / f1 = image n of the two views, into layer `layer` (of L) of ws (tnr_lpips_workspace_bytes(N, L)).
+ * tnr_lpips_finalize: out[n] (fp64) = sum over the L layers of the layer's sum / its pixel count; per_layer (optional, [N, L])
+ *   receives the terms.  Deterministic: bit-identical across runs; exactly 0 for identical features.                            */
+int tnr_lpips_stem_dims(int32_t H, int32_t W, int32_t crop, int32_t *Ho, int32_t *Wo);
+int tnr_lpips_stem(const void *a, const void *b, int32_t src_kind, int32_t N, int32_t H, int32_t W, int32_t C, int32_t crop,
+                   int32_t normalize, const float *shift, const float *scale, const float *w, const float *bias, tnr_view y,
+                   void *stream);
+int tnr_maxpool3s2_ceil_dims(int32_t H, int32_t W, int32_t *Ho, int32_t *Wo);
+int tnr_maxpool3s2_ceil_fwd(tnr_view x, tnr_view y, int32_t N, int32_t H, int32_t W, int32_t C, void *stream);
+int64_t tnr_lpips_workspace_bytes(int32_t N, int32_t L);
+int tnr_lpips_head(tnr_view f0, tnr_view f1, int32_t N, int32_t H, int32_t W, int32_t C, const float *w, int32_t layer, int32_t L,
+                   double *ws, int64_t ws_bytes, void *stream);
+int tnr_lpips_finalize(int32_t N, int32_t L, const double *ws, int64_t ws_bytes, double *out, double *per_layer, void *stream);
 /* Bilinear x2 up-sampling, align_corners = False, and its adjoint -- F.interpolate(x, scale_factor=2, mode='bilinear',
  * align_corners=False) between the decoder convolutions of UNetDiscriminator (discriminators.py:745-769).
  * fwd: x [N,H,W,C] -> y [N,2H,2W,C].  bwd: gy [N,2H,2W,C] -> gx (plain, may be null) and / or

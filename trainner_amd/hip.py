@@ -138,6 +138,13 @@ _SIGS = {
     "tnr_tensor2np_u8": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
     "tnr_metrics_workspace_bytes": (c_l, [c_i]),
     "tnr_psnr_ssim_u8": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_l, c_p]),
+    "tnr_lpips_stem_dims": (c_i, [c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i)]),
+    "tnr_lpips_stem": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, CView, c_p]),
+    "tnr_maxpool3s2_ceil_dims": (c_i, [c_i, c_i, C.POINTER(c_i), C.POINTER(c_i)]),
+    "tnr_maxpool3s2_ceil_fwd": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_p]),
+    "tnr_lpips_workspace_bytes": (c_l, [c_i, c_i]),
+    "tnr_lpips_head": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_l, c_p]),
+    "tnr_lpips_finalize": (c_i, [c_i, c_i, c_p, c_l, c_p, c_p, c_p]),
     "tnr_bilinear2x_fwd": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_p]),
     "tnr_bilinear2x_bwd": (c_i, [CView, CView, CView, CView, c_f, c_i, c_i, c_i, c_i, c_p]),
     "tnr_add2": (c_i, [CView, CView, CView, c_l, c_i, c_p]),

@@ -5,7 +5,8 @@ Same surface as the reference for what train.py uses (train.py:331-372,392-399):
 plus `calculate_psnr` / `calculate_ssim` on single images.  The images stay on the GPU as uint8 NHWC tensors
 (`trainner_amd.dataops.common.tensor2np`), PSNR is an exact integer sum of squares and SSIM an fp64 Gaussian-window
 reduction in libtrainner_hip.so (csrc/metrics.hip); one (sum, count) pair per image comes back to the host.
-LPIPS needs a pretrained network and is outside the engine (raises).
+'lpips' (net-lin / squeeze / v0.1, utils/metrics.py:37) runs on the same uint8 device images through
+models/modules/LPIPS (csrc/lpips.hip); it needs the two pretrained files that module names.
 """
 import math
 
@@ -66,14 +67,29 @@ def calculate_ssim(img1, img2, shave=4):
     return float(s[2]) / float(s[3])
 
 
+def _lpips_model(net="squeeze", use_gpu=False, spatial=False):
+    from ..models.modules.LPIPS import perceptual_loss
+    return perceptual_loss.PerceptualLoss(model="net-lin", net=net, use_gpu=use_gpu, spatial=spatial)
+
+
+def calculate_lpips(img1_im, img2_im, use_gpu=False, net="squeeze", spatial=False, model=None):
+    """utils/metrics.py:232-280: the mean LPIPS over the pairs (img1_im[i], img2_im[i]) of uint8 RGB images in [0, 255] (each HWC or
+    NHWC; an NHWC batch counts as that many pairs), as a 0-dim float64 tensor."""
+    if model is None:
+        model = _lpips_model(net, use_gpu, spatial)
+    d = [model.distance_u8(a, b) for a, b in zip(img1_im, img2_im)]
+    d = torch.cat(d)
+    return d.sum() / d.numel()
+
+
 class MetricsDict:
-    """utils/metrics.py:13-106 for 'psnr' and 'ssim'."""
+    """utils/metrics.py:13-106 for 'psnr', 'ssim' and 'lpips'."""
 
     def __init__(self, metrics="psnr", lpips_model=None):
         names = [m.strip().lower() for m in metrics.split(",") if m.strip()]
-        self.psnr, self.ssim = "psnr" in names, "ssim" in names
-        if "lpips" in names:
-            raise NotImplementedError("LPIPS validation metric is outside the SR hot path of the HIP engine")
+        self.psnr, self.ssim, self.lpips = "psnr" in names, "ssim" in names, "lpips" in names
+        if self.lpips:
+            self.lpips_model = lpips_model if lpips_model is not None else _lpips_model()
         self.metrics_list = [{"name": n} for n in names]
         self.reset()
 
@@ -81,13 +97,16 @@ class MetricsDict:
         self.count = 0
         self.psnr_sum = 0
         self.ssim_sum = 0
+        self.lpips_sum = 0
 
     def calculate_metrics(self, img1, img2, crop_size=4, only_y=False):
         if only_y:
             raise NotImplementedError("only_y metrics are not implemented by the HIP engine")
         s = psnr_ssim_sums(img1, img2, crop=crop_size, want_ssim=self.ssim)
+        lp = self.lpips_model.distance_u8(img1, img2, crop=crop_size) if self.lpips else None
         calculations = {}
         # one entry per image pair, like the reference (a batch counts as that many calls)
+        n0 = self.count
         for row in s:
             if self.psnr:
                 calculations["psnr"] = _psnr_from(float(row[0]), float(row[1]))
@@ -95,6 +114,9 @@ class MetricsDict:
             if self.ssim:
                 calculations["ssim"] = float(row[2]) / float(row[3])
                 self.ssim_sum += calculations["ssim"]
+            if self.lpips:
+                calculations["lpips"] = float(lp[self.count - n0])
+                self.lpips_sum += calculations["lpips"]
             self.count += 1
         return calculations
 
@@ -104,5 +126,7 @@ class MetricsDict:
             out["psnr"] = self.psnr_sum / self.count
         if self.ssim:
             out["ssim"] = self.ssim_sum / self.count
+        if self.lpips:
+            out["lpips"] = self.lpips_sum / self.count
         self.reset()
         return out
