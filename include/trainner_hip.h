@@ -512,6 +512,35 @@ int tnr_ragan_phase_c(const float *pf, const float *pr, int32_t n, int32_t stage
                       const float *sums, float *loss_out, float *gf, float *gr, void *stream);
 int tnr_scale_by(float *dst, const float *src, int64_t n, const float *gscale, void *stream);
 
+/* --- SSIM / MS-SSIM training losses (modules/ssim.py; get_loss_fn losses.py:70-85) --------------
+ * fp32 image batches x (carries the gradient) and y, N x C x H x W with 1..4 channels, layout 0 = NCHW-contiguous, 1 = channels-last.
+ * `shave` pixels are cut off every side first (their gradient is 0).  taps: K window taps on the HOST (K odd, <= 11), applied as a
+ * row pass then a column pass without padding, so the maps are (H - 2 shave - K + 1) x (W - 2 shave - K + 1).
+ * tnr_ssim_fwd: sums[n] = {sum ssim_map, sum cs_map} of image n over its C planes, fp64, fixed order (ws: tnr_ssim_workspace_bytes).
+ * tnr_ssim_bwd: gx (x's shape and layout; written, or added into when `accumulate`) = gscale[0] * sum over the maps of
+ *   coef[n][0] * d ssim_map / dx + coef[n][1] * d cs_map / dx; coef ([N][2]) and gscale (1 float, NULL = 1) are read on the device.
+ *   The moments are recomputed from x and y; sigma1_sq / sigma2_sq are clamped at 0 as ssim.py:181-182 (no gradient through a
+ *   clamped sigma1_sq).  y gets no gradient.
+ * tnr_avgpool2_pad_fwd: F.avg_pool2d(kernel 2, padding (h % 2, w % 2), count_include_pad) of the shaved x and y -> xo, yo, dense
+ *   NCHW [N, C, Ho, Wo] (tnr_avgpool2_pad_dims).  _bwd ADDS the pooled level's gradient gcoarse (dense NCHW) into gfine.
+ * tnr_msssim_combine: sums [levels][N][2] -> value (1 float) and coef [levels][N][2] for the levels' tnr_ssim_bwd calls.  counts
+ *   (elements per image of each level's maps) and weights are HOST arrays.  mode 0: SSIM, value = mean of the map over the batch
+ *   (levels = 1).  mode 1: MS-SSIM, normalize='relu', option 1 (ssim.py:394-399), mean over the batch; an image with a factor the
+ *   relu zeroed contributes the value 0 and the gradient 0. */
+int64_t tnr_ssim_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t shave, int32_t K);
+int tnr_ssim_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t shave,
+                 const float *taps, int32_t K, float C1, float C2, double *sums, void *ws, int64_t ws_bytes, void *stream);
+int tnr_ssim_bwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t shave,
+                 const float *taps, int32_t K, float C1, float C2, const float *coef, const float *gscale, float *gx,
+                 int32_t accumulate, void *stream);
+int tnr_avgpool2_pad_dims(int32_t H, int32_t W, int32_t shave, int32_t *Ho, int32_t *Wo);
+int tnr_avgpool2_pad_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t shave,
+                         float *xo, float *yo, void *stream);
+int tnr_avgpool2_pad_bwd(const float *gcoarse, float *gfine, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout,
+                         int32_t shave, void *stream);
+int tnr_msssim_combine(const double *sums, int32_t levels, int32_t N, const int64_t *counts, const float *weights, int32_t mode,
+                       float *value, float *coef, void *stream);
+
 /* --- optimiser (torch.optim.Adam optimizers.py:130-132; clip_grad_norm_ base_model.py:911-922) -- */
 int tnr_sumsq(const float *g, int64_t n, double *out, void *ws, void *stream);
 int tnr_clip_by_norm(float *g, int64_t n, const double *sumsq, float max_norm, void *stream);

@@ -170,6 +170,13 @@ _SIGS = {
     "tnr_ragan_phase_b": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
     "tnr_ragan_phase_c": (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "tnr_scale_by": (c_i, [c_p, c_p, c_l, c_p, c_p]),
+    "tnr_ssim_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "tnr_ssim_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_i, c_f, c_f, c_p, c_p, c_l, c_p]),
+    "tnr_ssim_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_i, c_f, c_f, c_p, c_p, c_p, c_i, c_p]),
+    "tnr_avgpool2_pad_dims": (c_i, [c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i)]),
+    "tnr_avgpool2_pad_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "tnr_avgpool2_pad_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "tnr_msssim_combine": (c_i, [c_p, c_i, c_i, C.POINTER(c_l), C.POINTER(c_f), c_i, c_p, c_p, c_p]),
     "tnr_sumsq": (c_i, [c_p, c_l, c_p, c_p, c_p]),
     "tnr_clip_by_norm": (c_i, [c_p, c_l, c_p, c_f, c_p]),
     "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),

@@ -119,6 +119,18 @@ class CycleGANModel(BaseModel):
         l_g_total = l_g_total + self._acc(sum(loss_results))
         loss_results, self.log_dict_B = self.generatorlosses(self.rec_B, self.real_B, self.log_dict_B, self.f_low)
         l_g_total = l_g_total + self._acc(sum(loss_results))
+        if self.use_idt and self.idtlosses.precise_loss_list:          # cyclegan_model.py:265-284
+            for idt, real, log in ((self.idt_A, self.real_B, self.log_dict_A), (self.idt_B, self.real_A, self.log_dict_B)):
+                tmp = LazyLog()
+                loss_idt, tmp = self.idtlosses(idt, real, tmp, self.f_low, precise=True)
+                l_g_total = l_g_total + self._acc(sum(loss_idt) * self.lambda_idt)
+                for k, v in tmp.items():
+                    log["{}_idt".format(k)] = v
+        if self.generatorlosses.precise_loss_list:                     # cyclegan_model.py:286-298
+            loss_results, self.log_dict_A = self.generatorlosses(self.rec_A, self.real_A, self.log_dict_A, self.f_low, precise=True)
+            l_g_total = l_g_total + self._acc(sum(loss_results))
+            loss_results, self.log_dict_B = self.generatorlosses(self.rec_B, self.real_B, self.log_dict_B, self.f_low, precise=True)
+            l_g_total = l_g_total + self._acc(sum(loss_results))
         # each generator appears 2 (+1 with the identity term) times in the graph: buckets leave in its last pass
         self._arm_bucket_schedule([self.netG_A, self.netG_B], passes=3 if self.use_idt else 2)
         self.calc_gradients(l_g_total)

@@ -4,14 +4,16 @@ Keeps the reference's surface (codes/models/losses.py): `get_loss_fn` -> {'name'
 `PerceptualLoss` (:220-340), `Adversarial` (:343-604) and `GeneratorLoss` (:607-962) with the same
 option keys, loss names (`pix-l1`, `fea-vgg19-l1`) and weighting order, restricted to the branches the
 ESRGAN recipe uses (options/sr/train_sr.yml:107-110,145-146): L1 pixel loss, VGG19 conv5_4 L1
-perceptual loss, vanilla relativistic GAN.  Anything else raises NotImplementedError (no silent
-fallback to eager PyTorch).
+perceptual loss, vanilla relativistic GAN, plus the SSIM / MS-SSIM term of the "precise" list
+(`ssim_type` / `ssim_weight`, losses.py:798-802).  Anything else raises NotImplementedError (no
+silent fallback to eager PyTorch).
 """
 import torch
 import torch.nn as nn
 
 from .. import hip, ops
 from . import networks
+from .modules.ssim import MS_SSIM, SSIM
 
 
 # ----------------------------------------------------------------------------------------------
@@ -159,6 +161,11 @@ def get_loss_fn(loss_type=None, weight=0, recurrent=False, reduction="mean", net
         fea_loss_f = get_loss_fn(parts[2], recurrent=True, reduction="mean", device=device)
         network = networks.define_F(opt).to(device)
         loss_function = PerceptualLoss(criterion=fea_loss_f, network=network, opt=opt)
+    elif loss_type in ("ssim", "SSIM", "ms-ssim", "MSSSIM"):
+        # losses.py:70-85; `opt` is the train block here (losses.py:799-801)
+        image_channels = ((opt or {}).get("image_channels") or 3) if allow_featnets else 1
+        kw = dict(window_size=11, window_sigma=1.5, size_average=True, data_range=1., channels=image_channels)
+        loss_function = SSIM(**kw) if loss_type in ("ssim", "SSIM") else MS_SSIM(normalize="relu", **kw)
     else:
         raise NotImplementedError("Loss type [{}] is not implemented by the HIP engine".format(loss_type))
     if recurrent:
@@ -292,7 +299,7 @@ class GeneratorLoss(nn.Module):
     """Weighted list of generator losses (losses.py:607-962): pixel then feature, same order/names."""
 
     _UNSUPPORTED = ("hfen_weight", "tv_weight", "color_weight", "avg_weight", "ms_weight", "spl_weight", "of_weight",
-                    "style_weight", "lpips_weight", "cx_weight", "grad_weight", "ssim_weight", "fft_weight",
+                    "style_weight", "lpips_weight", "cx_weight", "grad_weight", "fft_weight",
                     "fdpl_weight", "range_weight")
 
     def __init__(self, opt=None, device="cpu", allow_featnets=True):
@@ -316,14 +323,45 @@ class GeneratorLoss(nn.Module):
             self.cri_fea = True
         else:
             self.cri_fea = None
+        # the "precise" terms (losses.py:780-816), evaluated by the models after the GAN term and always in fp32
         self.precise_loss_list = []
+        ssim_weight = train_opt.get("ssim_weight", 0) or 0
+        ssim_type = train_opt.get("ssim_type", None)
+        if ssim_weight > 0 and ssim_type:
+            self.precise_loss_list.append(get_loss_fn(ssim_type, ssim_weight, opt=train_opt, allow_featnets=allow_featnets,
+                                                      device=device))
         self.dp_group = None        # set by SRModel when running data-parallel
+
+    def _log(self, log_dict, name, effective):
+        # under data parallelism the logged value is the global-batch mean, as the reference computes it on the gathered batch.
+        # The gradient needs no extra collective: every term here (L1, the VGG feature L1, SSIM, MS-SSIM) is a batch mean over
+        # equal shards, so averaging the ranks' gradients makes it the global-batch gradient
+        log_dict[name] = self.dp_group.mean_scalar(effective) if self.dp_group is not None else effective.detach()
+
+    def _forward_precise(self, sr, hr, log_dict):
+        """get_results_precise (losses.py:922-942): fp32 operands, then weight * (1 - f(sr, hr)) for the ssim terms."""
+        if sr.dtype in (torch.float16, torch.int8, torch.int32):
+            sr = sr.float()
+        if hr.dtype in (torch.float16, torch.int8, torch.int32):
+            hr = hr.float()
+        if sr.dtype != hr.dtype:
+            raise TypeError("Error: SR and HR have different precision in precise losses: {} and {}".format(sr.dtype, hr.dtype))
+        if sr.type() != hr.type():
+            raise TypeError("Error: SR and HR are on different devices in precise losses: {} and {}".format(sr.type(), hr.type()))
+        results = []
+        for l in self.precise_loss_list:
+            if "ssim" not in l["name"]:
+                raise NotImplementedError("precise loss [{}] is not implemented by the HIP engine".format(l["name"]))
+            effective = l["weight"] * (1 - l["function"](sr, hr))
+            results.append(effective)
+            self._log(log_dict, l["name"], effective)
+        return results, log_dict
 
     def forward(self, sr, hr, log_dict, fsfilter=None, selector=None, precise=False):
         if fsfilter is not None or selector:
             raise NotImplementedError("frequency separation / loss selectors are not implemented by the HIP engine")
         if precise:
-            return [], log_dict
+            return self._forward_precise(sr, hr, log_dict)
         results = []
         for l in self.loss_list:
             if "fea-vgg" in l["name"]:

@@ -74,6 +74,10 @@ class Pix2PixModel(BaseModel):
         loss_results, self.log_dict = self.generatorlosses(self.fake_B, self.real_B, self.log_dict, self.f_low)
         l_g = sum(loss_results)
         l_g_total = l_g_total + (l_g if self.accumulations == 1 else l_g / self.accumulations)
+        if self.generatorlosses.precise_loss_list:          # pix2pix_model.py:169-174
+            loss_results, self.log_dict = self.generatorlosses(self.fake_B, self.real_B, self.log_dict, self.f_low, precise=True)
+            l_g = sum(loss_results)
+            l_g_total = l_g_total + (l_g if self.accumulations == 1 else l_g / self.accumulations)
         self._arm_bucket_schedule([self.netG])
         self.calc_gradients(l_g_total)
 

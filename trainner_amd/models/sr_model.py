@@ -102,6 +102,12 @@ class SRModel(BaseModel):
             l_g_gan = self.adversarial(self.fake_H, self.var_ref, netD=self.netD, stage="generator", fsfilter=self.f_high)
             self.log_dict["l_g_gan"] = l_g_gan.detach()
             l_g_total = l_g_total + (l_g_gan if self.accumulations == 1 else l_g_gan / self.accumulations)
+        # the "precise" terms (SSIM / MS-SSIM), after the GAN term as in the reference (sr_model.py:180-185); they run fp32 kernels
+        # with or without `use_amp`.  An empty list issues nothing
+        if self.generatorlosses.precise_loss_list:
+            loss_results, self.log_dict = self.generatorlosses(self.fake_H, self.real_H, self.log_dict, self.f_low, precise=True)
+            l_g = sum(loss_results)
+            l_g_total = l_g_total + (l_g if self.accumulations == 1 else l_g / self.accumulations)
         # G's gradient buckets (67 MB) CAN leave for RCCL from inside its backward, on the side stream, with the dense blocks staying one
         # launch each next to the collectives (the dispensed four-wave sweep, ops.g_buckets_leave_in_backward).  That combination --
         # tile hand-offs inside a launch while RCCL kernels that wait for PEERS hold CUs -- has never run on more than one GPU, so it is

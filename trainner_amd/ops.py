@@ -1108,6 +1108,55 @@ def l1_mean_bwd(a, b, scale, gscale, ga, accumulate=False):
                                          int(accumulate), hip.stream()), "l1_mean_bwd")
 
 
+# SSIM / MS-SSIM training losses (csrc/ssim_loss.hip).  x, y: fp32 N x C x H x W in one dense layout (`layout` 0 NCHW-contiguous,
+# 1 channels-last); taps: the window as a sequence of K Python floats (already rounded to fp32).
+def _ssim_taps(taps):
+    return (C.c_float * len(taps))(*taps), len(taps)
+
+
+def ssim_fwd(x, y, layout, shave, taps, C1, C2, sums):
+    """sums[n] (fp64 [N, 2]) = {sum ssim_map, sum cs_map} of image n."""
+    lib = hip.load()
+    N, Ch, H, W = x.shape
+    arr, K = _ssim_taps(taps)
+    nbytes = lib.tnr_ssim_workspace_bytes(N, Ch, H, W, shave, K)
+    ws = WS.get("ssim@%x" % hip.stream(), nbytes, x.device)
+    hip.check(lib.tnr_ssim_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, shave, arr, K, C1, C2, sums.data_ptr(), ws.data_ptr(),
+                               ws.numel() * 8, hip.stream()), "ssim_fwd")
+
+
+def ssim_bwd(x, y, layout, shave, taps, C1, C2, coef, gscale, gx, accumulate=False):
+    N, Ch, H, W = x.shape
+    arr, K = _ssim_taps(taps)
+    hip.check(hip.load().tnr_ssim_bwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, shave, arr, K, C1, C2, coef.data_ptr(),
+                                      hip.ptr(gscale), gx.data_ptr(), int(accumulate), hip.stream()), "ssim_bwd")
+
+
+def avgpool2_pad_dims(H, W, shave=0):
+    ho, wo = C.c_int32(), C.c_int32()
+    hip.check(hip.load().tnr_avgpool2_pad_dims(H, W, shave, C.byref(ho), C.byref(wo)), "avgpool2_pad_dims")
+    return ho.value, wo.value
+
+
+def avgpool2_pad_fwd(x, y, layout, shave, xo, yo):
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_avgpool2_pad_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, shave, xo.data_ptr(), yo.data_ptr(),
+                                              hip.stream()), "avgpool2_pad_fwd")
+
+
+def avgpool2_pad_bwd(gcoarse, gfine, layout, shave):
+    N, Ch, H, W = gfine.shape
+    hip.check(hip.load().tnr_avgpool2_pad_bwd(gcoarse.data_ptr(), gfine.data_ptr(), N, Ch, H, W, layout, shave, hip.stream()),
+              "avgpool2_pad_bwd")
+
+
+def msssim_combine(sums, levels, N, counts, weights, mode, value, coef):
+    cnt = (C.c_int64 * levels)(*counts)
+    wts = (C.c_float * levels)(*weights) if weights is not None else None
+    hip.check(hip.load().tnr_msssim_combine(sums.data_ptr(), levels, N, cnt, wts, mode, value.data_ptr(), coef.data_ptr(),
+                                            hip.stream()), "msssim_combine")
+
+
 def _reduce_ws(dev):
     return WS.get("reduce@%x" % hip.stream(), hip.load().tnr_reduce_workspace_bytes(), dev)
 
