@@ -541,6 +541,33 @@ int tnr_avgpool2_pad_bwd(const float *gcoarse, float *gfine, int32_t N, int32_t 
 int tnr_msssim_combine(const double *sums, int32_t levels, int32_t N, const int64_t *counts, const float *weights, int32_t mode,
                        float *value, float *coef, void *stream);
 
+/* --- HFEN, image-gradient, total-variation and difference-only pixel losses (modules/loss.py:47-58,173-343,387-402) --------------
+ * All have the form  stencil -> criterion rho -> sum  over fp32 batches x (carries the gradient) and y, N x C x H x W, layout 0 =
+ * NCHW-contiguous, 1 = channels-last.  rho(e): L1 |e|, L2 e^2, CB sqrt(e^2 + 1e-12), ELASTIC 0.2 e^2 + 0.8 |e|, CLIPL1 clamp(|e|, 0, 10);
+ * rho' as autograd gives it (sign(0) = 0, the clamp passes the gradient on the closed interval).  Every forward writes
+ * loss[0] = scale * sum rho(e) (fp64 partials per block, summed in a fixed order; ws: tnr_imgloss_workspace_bytes); every backward
+ * writes gx (x's shape and layout), or adds into it when `accumulate`, times scale * gscale[0] (1 float on the device, NULL = 1).
+ * tnr_filter_loss_*: e = L * (x - y), the zero-padded K x K correlation (K odd, <= 15, taps row-major on the HOST, the same for every
+ *   channel).  fwd also stores rho'(e) into dmap (x's layout) unless it is NULL; bwd applies the adjoint stencil to such a map.
+ * tnr_fd_loss_*: e = dir(x) - dir(y) over the dirs = 2 (dx, dy) or 4 (dx, dy, dp, dn) one-step finite differences of
+ *   dataops/filters.py:722-777 as they are: dx is zeroed in the last column, dy and dp in the last row, dn = x[i+1][j+1] - x[i][j] is
+ *   not, and dp = right - bottom sees a zero `right` in the last column.  y == NULL means dir(y) = 0 (total variation).  bwd
+ *   recomputes the responses; no map is kept.
+ * tnr_pointwise_loss_*: e = a - b over n elements of any dense layout (ws: tnr_reduce_workspace_bytes). */
+enum { TNR_CRIT_L1 = 0, TNR_CRIT_L2 = 1, TNR_CRIT_CB = 2, TNR_CRIT_ELASTIC = 3, TNR_CRIT_CLIPL1 = 4 };
+int64_t tnr_imgloss_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int tnr_filter_loss_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const float *taps,
+                        int32_t K, int32_t crit, double scale, float *loss, float *dmap, void *ws, int64_t ws_bytes, void *stream);
+int tnr_filter_loss_bwd(const float *dmap, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const float *taps, int32_t K,
+                        double scale, const float *gscale, float *gx, int32_t accumulate, void *stream);
+int tnr_fd_loss_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t dirs,
+                    int32_t crit, double scale, float *loss, void *ws, int64_t ws_bytes, void *stream);
+int tnr_fd_loss_bwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t dirs,
+                    int32_t crit, double scale, const float *gscale, float *gx, int32_t accumulate, void *stream);
+int tnr_pointwise_loss_fwd(const float *a, const float *b, int64_t n, int32_t crit, double scale, float *loss, void *ws, void *stream);
+int tnr_pointwise_loss_bwd(const float *a, const float *b, int64_t n, int32_t crit, double scale, const float *gscale, float *ga,
+                           int32_t accumulate, void *stream);
+
 /* --- optimiser (torch.optim.Adam optimizers.py:130-132; clip_grad_norm_ base_model.py:911-922) -- */
 int tnr_sumsq(const float *g, int64_t n, double *out, void *ws, void *stream);
 int tnr_clip_by_norm(float *g, int64_t n, const double *sumsq, float max_norm, void *stream);

@@ -177,6 +177,13 @@ _SIGS = {
     "tnr_avgpool2_pad_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "tnr_avgpool2_pad_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "tnr_msssim_combine": (c_i, [c_p, c_i, c_i, C.POINTER(c_l), C.POINTER(c_f), c_i, c_p, c_p, c_p]),
+    "tnr_imgloss_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i]),
+    "tnr_filter_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_i, c_i, C.c_double, c_p, c_p, c_p, c_l, c_p]),
+    "tnr_filter_loss_bwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_i, C.c_double, c_p, c_p, c_i, c_p]),
+    "tnr_fd_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, C.c_double, c_p, c_p, c_l, c_p]),
+    "tnr_fd_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, C.c_double, c_p, c_p, c_i, c_p]),
+    "tnr_pointwise_loss_fwd": (c_i, [c_p, c_p, c_l, c_i, C.c_double, c_p, c_p, c_p]),
+    "tnr_pointwise_loss_bwd": (c_i, [c_p, c_p, c_l, c_i, C.c_double, c_p, c_p, c_i, c_p]),
     "tnr_sumsq": (c_i, [c_p, c_l, c_p, c_p, c_p]),
     "tnr_clip_by_norm": (c_i, [c_p, c_l, c_p, c_f, c_p]),
     "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),

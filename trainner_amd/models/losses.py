@@ -5,14 +5,17 @@ Keeps the reference's surface (codes/models/losses.py): `get_loss_fn` -> {'name'
 option keys, loss names (`pix-l1`, `fea-vgg19-l1`) and weighting order, restricted to the branches the
 ESRGAN recipe uses (options/sr/train_sr.yml:107-110,145-146): L1 pixel loss, VGG19 conv5_4 L1
 perceptual loss, vanilla relativistic GAN, plus the SSIM / MS-SSIM term of the "precise" list
-(`ssim_type` / `ssim_weight`, losses.py:798-802).  Anything else raises NotImplementedError (no
-silent fallback to eager PyTorch).
+(`ssim_type` / `ssim_weight`, losses.py:798-802) and the recipe's edge / smoothness terms
+(train_sr.yml:114-120): the difference-only pixel criteria l2, cb, elastic and clipl1, HFEN (`hfen_criterion` /
+`hfen_weight`), total variation (`tv_type` / `tv_norm` / `tv_weight`) and the image-gradient loss of the precise list
+(`grad_type` / `grad_weight`).  Anything else raises NotImplementedError (no silent fallback to eager PyTorch).
 """
 import torch
 import torch.nn as nn
 
 from .. import hip, ops
 from . import networks
+from .modules import image_losses as IL
 from .modules.ssim import MS_SSIM, SSIM
 
 
@@ -154,10 +157,28 @@ def get_loss_fn(loss_type=None, weight=0, recurrent=False, reduction="mean", net
     if loss_type in ("L1", "l1"):
         loss_function = L1Loss(reduction=reduction)
         loss_type = "pix-{}".format(loss_type)
+    elif loss_type in ("MSE", "l2", "cb", "elastic", "clipl1"):
+        loss_function = IL.criterion(loss_type, reduction)
+        loss_type = "pix-{}".format(loss_type)
+    elif loss_type is not None and loss_type.find("hfen") >= 0:
+        # losses.py:86-92: the criterion is asked for with reduction='sum' (cb and clipl1 ignore it and stay means)
+        loss_function = IL.HFENLoss(loss_f=IL.criterion(loss_type.split("-")[1], "sum"))
+    elif loss_type is not None and loss_type.find("grad") >= 0:
+        parts = loss_type.split("-")            # grad-2d-<criterion> | grad-4d-<criterion> (losses.py:93-99)
+        if len(parts) != 3:
+            raise NotImplementedError("Loss type [{}] is not implemented by the HIP engine".format(loss_type))
+        loss_function = IL.GradientLoss(loss_f=IL.criterion(parts[2]), gradientdir=parts[1])
+    elif loss_type is not None and loss_type.find("tv") >= 0:
+        parts = loss_type.split("-")            # tv-l1 | tv-l2 | dtv-l1 | dtv-l2 (losses.py:111-116)
+        if len(parts) != 2 or parts[0] not in ("tv", "dtv") or parts[1] not in ("l1", "l2"):
+            raise NotImplementedError("Loss type [{}] is not implemented by the HIP engine".format(loss_type))
+        loss_function = IL.TVLoss(tv_type=parts[0], p=parts[1])
     elif loss_type is not None and loss_type.find("fea") >= 0:
         parts = loss_type.split("-")
         if parts[1] == "lpips":
             raise NotImplementedError("LPIPS is outside the SR hot path of the HIP engine")
+        if parts[2] not in ("L1", "l1"):
+            raise NotImplementedError("feature criterion [{}] is not implemented by the HIP engine (l1 only)".format(parts[2]))
         fea_loss_f = get_loss_fn(parts[2], recurrent=True, reduction="mean", device=device)
         network = networks.define_F(opt).to(device)
         loss_function = PerceptualLoss(criterion=fea_loss_f, network=network, opt=opt)
@@ -173,10 +194,24 @@ def get_loss_fn(loss_type=None, weight=0, recurrent=False, reduction="mean", net
     return {"name": loss_type, "weight": weight, "function": loss_function.to(device)}
 
 
-def check_loss_names(feature_criterion=None, feature_network=None, **_unused):
-    """losses.py:174-217 for the feature-loss name only."""
+def check_loss_names(feature_criterion=None, feature_network=None, hfen_criterion=None, tv_type=None, tv_norm=None, **_unused):
+    """losses.py:174-217 for the feature, HFEN and total-variation names."""
     if feature_criterion and feature_network:
         return "fea-{}-{}".format(feature_network.lower(), feature_criterion.lower())
+    if hfen_criterion:
+        if hfen_criterion in ("rel_l1", "rel_l2"):
+            return "hfen-relativel1"
+        return "hfen-{}".format(hfen_criterion.lower())
+    if tv_type and tv_norm:           # a tv_type without a tv_norm names nothing, as in the reference
+        if tv_norm in (1, "L1"):
+            tv_norm = "l1"
+        elif tv_norm in (2, "L2"):
+            tv_norm = "l2"
+        if tv_type == "normal":
+            tv_type = "tv"
+        elif tv_type == "4D":
+            tv_type = "dtv"
+        return "{}-{}".format(tv_type, tv_norm)
     return None
 
 
@@ -296,10 +331,11 @@ def ops_mean(pred):
 
 
 class GeneratorLoss(nn.Module):
-    """Weighted list of generator losses (losses.py:607-962): pixel then feature, same order/names."""
+    """Weighted list of generator losses (losses.py:607-962): pixel, hfen, tv, feature, then the precise list grad, ssim; same
+    order and names."""
 
-    _UNSUPPORTED = ("hfen_weight", "tv_weight", "color_weight", "avg_weight", "ms_weight", "spl_weight", "of_weight",
-                    "style_weight", "lpips_weight", "cx_weight", "grad_weight", "fft_weight",
+    _UNSUPPORTED = ("color_weight", "avg_weight", "ms_weight", "spl_weight", "of_weight",
+                    "style_weight", "lpips_weight", "cx_weight", "fft_weight",
                     "fdpl_weight", "range_weight")
 
     def __init__(self, opt=None, device="cpu", allow_featnets=True):
@@ -313,6 +349,14 @@ class GeneratorLoss(nn.Module):
         self.loss_list = []
         if pixel_weight > 0 and pixel_criterion:
             self.loss_list.append(get_loss_fn(pixel_criterion, pixel_weight, device=device))
+        hfen_weight = train_opt.get("hfen_weight", 0) or 0
+        hfen_criterion = check_loss_names(hfen_criterion=train_opt.get("hfen_criterion"))
+        if hfen_weight > 0 and hfen_criterion:
+            self.loss_list.append(get_loss_fn(hfen_criterion, hfen_weight, device=device))
+        tv_weight = train_opt.get("tv_weight", 0) or 0
+        tv_type = check_loss_names(tv_type=train_opt.get("tv_type"), tv_norm=train_opt.get("tv_norm"))
+        if tv_weight > 0 and tv_type:
+            self.loss_list.append(get_loss_fn(tv_type, tv_weight, device=device))
         feature_weight = (train_opt.get("feature_weight", 0) or 0) if allow_featnets else 0
         feat_opts = train_opt.get("perceptual_opt")
         feature_network = (feat_opts or {}).get("feature_network", None) or train_opt.get("feature_network", "vgg19") or "vgg19"
@@ -325,6 +369,15 @@ class GeneratorLoss(nn.Module):
             self.cri_fea = None
         # the "precise" terms (losses.py:780-816), evaluated by the models after the GAN term and always in fp32
         self.precise_loss_list = []
+        grad_weight = train_opt.get("grad_weight", 0) or 0
+        grad_type = train_opt.get("grad_type", None)
+        if grad_weight > 0 and not grad_type:
+            # the one place where the engine is stricter than the reference, which silently builds nothing here: a grad weight
+            # without a type is refused
+            raise NotImplementedError("loss option 'grad_weight' is set but 'grad_type' is not: give grad_type "
+                                      "(grad-2d-<criterion> | grad-4d-<criterion>) or drop the weight")
+        if grad_weight > 0:
+            self.precise_loss_list.append(get_loss_fn(grad_type, grad_weight, device=device))
         ssim_weight = train_opt.get("ssim_weight", 0) or 0
         ssim_type = train_opt.get("ssim_type", None)
         if ssim_weight > 0 and ssim_type:
@@ -332,27 +385,42 @@ class GeneratorLoss(nn.Module):
                                                       device=device))
         self.dp_group = None        # set by SRModel when running data-parallel
 
+    def _effective(self, l, value):
+        """weight * value; a batch SUM (HFEN with a sum-reduced criterion: hfen-l1, hfen-l2, hfen-elastic) is also multiplied by the
+        world size under data parallelism, because the reference sums over the gathered global batch: the ranks' averaged gradient
+        is then the global one and the averaged log entry the global sum."""
+        effective = l["weight"] * value
+        if self.dp_group is not None and getattr(l["function"], "sum_reduced", False):
+            effective = effective * float(self.dp_group.world_size)
+        return effective
+
     def _log(self, log_dict, name, effective):
         # under data parallelism the logged value is the global-batch mean, as the reference computes it on the gathered batch.
-        # The gradient needs no extra collective: every term here (L1, the VGG feature L1, SSIM, MS-SSIM) is a batch mean over
-        # equal shards, so averaging the ranks' gradients makes it the global-batch gradient
+        # The gradient needs no extra collective: every term here but the sum-reduced HFEN ones (see _effective) is a batch mean
+        # over equal shards, so averaging the ranks' gradients makes it the global-batch gradient
         log_dict[name] = self.dp_group.mean_scalar(effective) if self.dp_group is not None else effective.detach()
 
+    @staticmethod
+    def _fp32(t):
+        """The operand every fp32 loss kernel reads: half and integer types are promoted (losses.py:935-938; bfloat16 added)."""
+        return t.float() if t.dtype in (torch.float16, torch.bfloat16, torch.int8, torch.int32) else t
+
     def _forward_precise(self, sr, hr, log_dict):
-        """get_results_precise (losses.py:922-942): fp32 operands, then weight * (1 - f(sr, hr)) for the ssim terms."""
-        if sr.dtype in (torch.float16, torch.int8, torch.int32):
-            sr = sr.float()
-        if hr.dtype in (torch.float16, torch.int8, torch.int32):
-            hr = hr.float()
+        """get_results_precise (losses.py:922-942): fp32 operands, then weight * (1 - f(sr, hr)) for the ssim terms and
+        weight * f(sr, hr) for the gradient loss."""
+        sr, hr = self._fp32(sr), self._fp32(hr)
         if sr.dtype != hr.dtype:
             raise TypeError("Error: SR and HR have different precision in precise losses: {} and {}".format(sr.dtype, hr.dtype))
         if sr.type() != hr.type():
             raise TypeError("Error: SR and HR are on different devices in precise losses: {} and {}".format(sr.type(), hr.type()))
         results = []
         for l in self.precise_loss_list:
-            if "ssim" not in l["name"]:
+            if "ssim" in l["name"]:
+                effective = l["weight"] * (1 - l["function"](sr, hr))
+            elif "grad" in l["name"]:
+                effective = self._effective(l, l["function"](sr, hr))
+            else:
                 raise NotImplementedError("precise loss [{}] is not implemented by the HIP engine".format(l["name"]))
-            effective = l["weight"] * (1 - l["function"](sr, hr))
             results.append(effective)
             self._log(log_dict, l["name"], effective)
         return results, log_dict
@@ -367,10 +435,12 @@ class GeneratorLoss(nn.Module):
             if "fea-vgg" in l["name"]:
                 percep_loss, _ = l["function"](sr, hr)
                 effective = l["weight"] * percep_loss
+            elif "tv" in l["name"]:
+                effective = self._effective(l, l["function"](self._fp32(sr)))              # fake_H alone
+            elif isinstance(l["function"], (IL.HFENLoss, IL._Criterion)):
+                effective = self._effective(l, l["function"](self._fp32(sr), self._fp32(hr)))   # fp32 kernels with or without AMP
             else:
                 effective = l["weight"] * l["function"](sr, hr)
             results.append(effective)
-            # under data parallelism the logged value is the global-batch mean, as the reference computes it on the
-            # gathered batch (the gradient uses the local mean: averaging over ranks makes it the global one)
-            log_dict[l["name"]] = self.dp_group.mean_scalar(effective) if self.dp_group is not None else effective.detach()
+            self._log(log_dict, l["name"], effective)
         return results, log_dict

@@ -1157,6 +1157,56 @@ def msssim_combine(sums, levels, N, counts, weights, mode, value, coef):
                                             hip.stream()), "msssim_combine")
 
 
+# HFEN / image-gradient / total-variation / difference-only pixel losses (csrc/image_losses.hip).  x, y as for the ssim wrappers;
+# crit: one of the CRIT_* numbers; every forward writes loss (1 float) = scale * sum rho(e), every backward gx (x's layout) =
+# scale * gscale[0] * d sum rho / dx (gscale None = 1).
+CRIT_L1, CRIT_L2, CRIT_CB, CRIT_ELASTIC, CRIT_CLIPL1 = 0, 1, 2, 3, 4
+
+
+def _imgloss_ws(x):
+    N, Ch, H, W = x.shape
+    return WS.get("imgloss@%x" % hip.stream(), hip.load().tnr_imgloss_workspace_bytes(N, Ch, H, W), x.device)
+
+
+def filter_loss_fwd(x, y, layout, taps, K, crit, scale, loss, dmap=None):
+    """taps: K * K Python floats, row-major.  dmap (x's shape and layout, or None) receives rho'(L * (x - y))."""
+    N, Ch, H, W = x.shape
+    ws = _imgloss_ws(x)
+    hip.check(hip.load().tnr_filter_loss_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, (C.c_float * (K * K))(*taps), K, crit,
+                                             float(scale), loss.data_ptr(), hip.ptr(dmap), ws.data_ptr(), ws.numel() * 8, hip.stream()),
+              "filter_loss_fwd")
+
+
+def filter_loss_bwd(dmap, layout, taps, K, scale, gscale, gx, accumulate=False):
+    N, Ch, H, W = dmap.shape
+    hip.check(hip.load().tnr_filter_loss_bwd(dmap.data_ptr(), N, Ch, H, W, layout, (C.c_float * (K * K))(*taps), K, float(scale),
+                                             hip.ptr(gscale), gx.data_ptr(), int(accumulate), hip.stream()), "filter_loss_bwd")
+
+
+def fd_loss_fwd(x, y, layout, dirs, crit, scale, loss):
+    """y None: the responses of x alone (total variation)."""
+    N, Ch, H, W = x.shape
+    ws = _imgloss_ws(x)
+    hip.check(hip.load().tnr_fd_loss_fwd(x.data_ptr(), hip.ptr(y), N, Ch, H, W, layout, dirs, crit, float(scale), loss.data_ptr(),
+                                         ws.data_ptr(), ws.numel() * 8, hip.stream()), "fd_loss_fwd")
+
+
+def fd_loss_bwd(x, y, layout, dirs, crit, scale, gscale, gx, accumulate=False):
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_fd_loss_bwd(x.data_ptr(), hip.ptr(y), N, Ch, H, W, layout, dirs, crit, float(scale), hip.ptr(gscale),
+                                         gx.data_ptr(), int(accumulate), hip.stream()), "fd_loss_bwd")
+
+
+def pointwise_loss_fwd(a, b, crit, scale, loss):
+    hip.check(hip.load().tnr_pointwise_loss_fwd(a.data_ptr(), b.data_ptr(), a.numel(), crit, float(scale), loss.data_ptr(),
+                                                _reduce_ws(a.device).data_ptr(), hip.stream()), "pointwise_loss_fwd")
+
+
+def pointwise_loss_bwd(a, b, crit, scale, gscale, ga, accumulate=False):
+    hip.check(hip.load().tnr_pointwise_loss_bwd(a.data_ptr(), b.data_ptr(), a.numel(), crit, float(scale), hip.ptr(gscale), ga.data_ptr(),
+                                                int(accumulate), hip.stream()), "pointwise_loss_bwd")
+
+
 def _reduce_ws(dev):
     return WS.get("reduce@%x" % hip.stream(), hip.load().tnr_reduce_workspace_bytes(), dev)
 
