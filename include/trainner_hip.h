@@ -568,6 +568,22 @@ int tnr_pointwise_loss_fwd(const float *a, const float *b, int64_t n, int32_t cr
 int tnr_pointwise_loss_bwd(const float *a, const float *b, int64_t n, int32_t crit, double scale, const float *gscale, float *ga,
                            int32_t accumulate, void *stream);
 
+/* --- frequency separation (dataops/filters.py FilterLow :643-671, FilterHigh :674-717; csrc/freqsep.hip) ---------------------------
+ * L = the zero-padded 9 x 9 low-pass of a fp32 batch N x C x H x W (layout 0 = NCHW-contiguous, 1 = channels-last), evaluated
+ * separably from the 9 taps `taps9` on the HOST (2-D taps = their outer product; average: 1/9 each; Gaussian: sigma 1.5, normalised).
+ * One launch each; no workspace; out / gx have x's shape and layout and must not alias an input.
+ * tnr_freqsep_low: out = gscale[0] * (L x), or out += that when `accumulate` (gscale: 1 float on the device, NULL = 1).  L is its own
+ *   adjoint, so this is FilterLow's forward and its backward.
+ * tnr_freqsep_high_fwd: out = clamp((x - L x + 1) / 2, 0, 1), the "separator" FilterHigh with normalize=True.
+ * tnr_freqsep_high_bwd: g' = 0.5 g where the forward's saved output o lies strictly inside (0, 1), else 0;
+ *   gx = gscale[0] * (g' - L g'), or gx += that when `accumulate`. */
+int tnr_freqsep_low(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const float *taps9, const float *gscale,
+                    float *out, int32_t accumulate, void *stream);
+int tnr_freqsep_high_fwd(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const float *taps9, float *out,
+                         void *stream);
+int tnr_freqsep_high_bwd(const float *g, const float *o, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const float *taps9,
+                         const float *gscale, float *gx, int32_t accumulate, void *stream);
+
 /* --- optimiser (torch.optim.Adam optimizers.py:130-132; clip_grad_norm_ base_model.py:911-922) -- */
 int tnr_sumsq(const float *g, int64_t n, double *out, void *ws, void *stream);
 int tnr_clip_by_norm(float *g, int64_t n, const double *sumsq, float max_norm, void *stream);

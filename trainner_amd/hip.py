@@ -184,6 +184,9 @@ _SIGS = {
     "tnr_fd_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, C.c_double, c_p, c_p, c_i, c_p]),
     "tnr_pointwise_loss_fwd": (c_i, [c_p, c_p, c_l, c_i, C.c_double, c_p, c_p, c_p]),
     "tnr_pointwise_loss_bwd": (c_i, [c_p, c_p, c_l, c_i, C.c_double, c_p, c_p, c_i, c_p]),
+    "tnr_freqsep_low": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),
+    "tnr_freqsep_high_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p]),
+    "tnr_freqsep_high_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),
     "tnr_sumsq": (c_i, [c_p, c_l, c_p, c_p, c_p]),
     "tnr_clip_by_norm": (c_i, [c_p, c_l, c_p, c_f, c_p]),
     "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),

@@ -38,6 +38,9 @@ def training_step(fn):
             net = getattr(self, "net" + name, None)
             if net is not None and hasattr(net, "memo_clear"):
                 net.memo_clear()
+        for f in (getattr(self, "f_low", None), getattr(self, "f_high", None)):      # the filters' per-step memos: same lifetime
+            if f is not None:
+                f.memo_clear()
         with self.amp_region():
             return fn(self, step, *a, **kw)
     return wrapped
@@ -271,8 +274,15 @@ class BaseModel:
         self._reject(self.opt["train"].get("mixup"), "batch augmentation (mixup)")
 
     def setup_fs(self):
+        """base_model.py:629-639: `fs` switches frequency separation on; `lpf_type` / `hpf_type` (default average) pick the filters."""
         self.f_low = self.f_high = None
-        self._reject(self.opt["train"].get("fs"), "frequency separation (fs)")
+        train_opt = self.opt["train"]
+        self.fs = train_opt.get("fs")
+        if self.fs:
+            from ..dataops.filters import FilterHigh, FilterLow
+            self.f_low = FilterLow(filter_type=train_opt.get("lpf_type", "average")).to(self.device)
+            self.f_high = FilterHigh(filter_type=train_opt.get("hpf_type", "average")).to(self.device)
+            logger.info("Frequency separation enabled")
 
     def setup_gan(self, conditional=False):
         train_opt = self.opt["train"]

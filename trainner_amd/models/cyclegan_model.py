@@ -53,6 +53,9 @@ class CycleGANModel(BaseModel):
             self.fake_A_pool = ImagePool(opt["pool_size"])
             self.fake_B_pool = ImagePool(opt["pool_size"])
             self.setup_batchaug()
+            if train_opt.get("fs"):
+                raise NotImplementedError("frequency separation (fs) with the CycleGAN model is not implemented by the HIP engine "
+                                          "(the SR and Pix2Pix models take it)")
             self.setup_fs()
             self.generatorlosses = losses.GeneratorLoss(opt, self.device)
             self.generatorlosses.dp_group = self.dp if self.dp.active else None

@@ -8,12 +8,15 @@ perceptual loss, vanilla relativistic GAN, plus the SSIM / MS-SSIM term of the "
 (`ssim_type` / `ssim_weight`, losses.py:798-802) and the recipe's edge / smoothness terms
 (train_sr.yml:114-120): the difference-only pixel criteria l2, cb, elastic and clipl1, HFEN (`hfen_criterion` /
 `hfen_weight`), total variation (`tv_type` / `tv_norm` / `tv_weight`) and the image-gradient loss of the precise list
-(`grad_type` / `grad_weight`).  Anything else raises NotImplementedError (no silent fallback to eager PyTorch).
+(`grad_type` / `grad_weight`).  With frequency separation (`fs`, base_model.setup_fs) `GeneratorLoss` hands the low-passed images to
+the colour / content terms and `Adversarial` shows the discriminator the high-pass residual (dataops/filters.py).  Anything else
+raises NotImplementedError (no silent fallback to eager PyTorch).
 """
 import torch
 import torch.nn as nn
 
 from .. import hip, ops
+from ..dataops import filters
 from . import networks
 from .modules import image_losses as IL
 from .modules.ssim import MS_SSIM, SSIM
@@ -283,7 +286,13 @@ class Adversarial(nn.Module):
 
     def forward(self, fake, real=None, condition=None, netD=None, stage="discriminator", fsfilter=None):
         if fsfilter is not None:
-            raise NotImplementedError("frequency separation is not implemented by the HIP engine")
+            # losses.py:572-576: both images through the high-pass, in both stages and BEFORE the conditional concatenation (the
+            # condition image is not filtered).  The discriminator stage filters fake.detach(): no graph is needed there, and the
+            # filter's per-step memo hands back the generator stage's result, so netD's forward memo still hits
+            _engine_filter(fsfilter, filters.FilterHigh)
+            fake = fsfilter(fake if stage == "generator" else fake.detach())
+            if isinstance(real, torch.Tensor):
+                real = fsfilter(real)
         if self.conditional:
             # like the reference's dispatch (losses.py:590-604) the second positional argument is the condition in the
             # generator stage (pix2pix_model.py:152-154 passes it by keyword)
@@ -320,6 +329,13 @@ class Adversarial(nn.Module):
         gan_logs = {"l_d_real": res[1].detach(), "l_d_fake": res[2].detach(),
                     "D_real": res[3].detach(), "D_fake": res[4].detach()}
         return res[0], gan_logs
+
+
+def _engine_filter(fsfilter, kind):
+    """Frequency separation runs through the engine's own filter modules only: any other callable would be an eager-PyTorch filter."""
+    if not isinstance(fsfilter, kind):
+        raise NotImplementedError("fsfilter must be a trainner_amd.dataops.filters.{} (built by BaseModel.setup_fs); other frequency-"
+                                  "separation filters are not implemented by the HIP engine".format(kind.__name__))
 
 
 def ops_mean(pred):
@@ -405,7 +421,38 @@ class GeneratorLoss(nn.Module):
         """The operand every fp32 loss kernel reads: half and integer types are promoted (losses.py:935-938; bfloat16 added)."""
         return t.float() if t.dtype in (torch.float16, torch.bfloat16, torch.int8, torch.int32) else t
 
-    def _forward_precise(self, sr, hr, log_dict):
+    def _forward_fs(self, loss_list, sr, hr, log_dict, fsfilter):
+        """calc_losses_fs (losses.py:865-899) for either list: the operands go by the loss NAME.  sr_f / hr_f are formed on first use
+        (not at all when no term of the list consumes them) and shared by every term; the filter's per-step memo also shares them
+        between the regular and the precise call, so one adjoint launch carries the summed gradient."""
+        low = {}
+
+        def lp(tag, t):
+            if tag not in low:
+                low[tag] = fsfilter(self._fp32(t))
+            return low[tag]
+
+        results = []
+        for l in loss_list:
+            name, f = l["name"], l["function"]
+            if "tv" in name:
+                effective = self._effective(l, f(lp("sr", sr)))                     # fake_H alone
+            elif "pix" in name or "hfen" in name:
+                effective = self._effective(l, f(lp("sr", sr), lp("hr", hr)))
+            elif "ssim" in name:
+                effective = l["weight"] * (1 - f(lp("sr", sr), lp("hr", hr)))
+            elif "fea-vgg" in name:
+                percep_loss, _ = f(sr, hr)                                          # unfiltered
+                effective = l["weight"] * percep_loss
+            else:
+                # everything else sees the unfiltered pair.  That includes grad-2d-* / grad-4d-*: the reference's low-pass branch asks
+                # for 'gradient' in the name (losses.py:879), which these names do not contain -- its quirk, kept
+                effective = self._effective(l, f(self._fp32(sr), self._fp32(hr)))
+            results.append(effective)
+            self._log(log_dict, name, effective)
+        return results, log_dict
+
+    def _forward_precise(self, sr, hr, log_dict, fsfilter=None):
         """get_results_precise (losses.py:922-942): fp32 operands, then weight * (1 - f(sr, hr)) for the ssim terms and
         weight * f(sr, hr) for the gradient loss."""
         sr, hr = self._fp32(sr), self._fp32(hr)
@@ -413,6 +460,8 @@ class GeneratorLoss(nn.Module):
             raise TypeError("Error: SR and HR have different precision in precise losses: {} and {}".format(sr.dtype, hr.dtype))
         if sr.type() != hr.type():
             raise TypeError("Error: SR and HR are on different devices in precise losses: {} and {}".format(sr.type(), hr.type()))
+        if fsfilter is not None:
+            return self._forward_fs(self.precise_loss_list, sr, hr, log_dict, fsfilter)
         results = []
         for l in self.precise_loss_list:
             if "ssim" in l["name"]:
@@ -426,10 +475,14 @@ class GeneratorLoss(nn.Module):
         return results, log_dict
 
     def forward(self, sr, hr, log_dict, fsfilter=None, selector=None, precise=False):
-        if fsfilter is not None or selector:
-            raise NotImplementedError("frequency separation / loss selectors are not implemented by the HIP engine")
+        if selector:
+            raise NotImplementedError("loss selectors are not implemented by the HIP engine")
+        if fsfilter is not None:
+            _engine_filter(fsfilter, filters.FilterLow)
         if precise:
-            return self._forward_precise(sr, hr, log_dict)
+            return self._forward_precise(sr, hr, log_dict, fsfilter)
+        if fsfilter is not None:
+            return self._forward_fs(self.loss_list, sr, hr, log_dict, fsfilter)
         results = []
         for l in self.loss_list:
             if "fea-vgg" in l["name"]:

@@ -1207,6 +1207,28 @@ def pointwise_loss_bwd(a, b, crit, scale, gscale, ga, accumulate=False):
                                                 int(accumulate), hip.stream()), "pointwise_loss_bwd")
 
 
+# Frequency separation (csrc/freqsep.hip): the zero-padded 9 x 9 low-pass L from its 9 separable taps (Python floats) and the
+# separator high-pass clamp((x - L x + 1) / 2, 0, 1).  x / g / o / out: fp32 N x C x H x W in one dense layout; one launch each.
+def freqsep_low(x, layout, taps9, out, gscale=None, accumulate=False):
+    """out (+)= gscale[0] * (L x): FilterLow's forward and, L being its own adjoint, its backward."""
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_freqsep_low(x.data_ptr(), N, Ch, H, W, layout, (C.c_float * 9)(*taps9), hip.ptr(gscale), out.data_ptr(),
+                                         int(accumulate), hip.stream()), "freqsep_low")
+
+
+def freqsep_high_fwd(x, layout, taps9, out):
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_freqsep_high_fwd(x.data_ptr(), N, Ch, H, W, layout, (C.c_float * 9)(*taps9), out.data_ptr(), hip.stream()),
+              "freqsep_high_fwd")
+
+
+def freqsep_high_bwd(g, o, layout, taps9, gx, gscale=None, accumulate=False):
+    """gx (+)= gscale[0] * (g' - L g'), g' = 0.5 g where the forward's saved output o is strictly inside (0, 1)."""
+    N, Ch, H, W = g.shape
+    hip.check(hip.load().tnr_freqsep_high_bwd(g.data_ptr(), o.data_ptr(), N, Ch, H, W, layout, (C.c_float * 9)(*taps9), hip.ptr(gscale),
+                                              gx.data_ptr(), int(accumulate), hip.stream()), "freqsep_high_bwd")
+
+
 def _reduce_ws(dev):
     return WS.get("reduce@%x" % hip.stream(), hip.load().tnr_reduce_workspace_bytes(), dev)
 
