@@ -30,6 +30,22 @@ static inline int tnr_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t tnr_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int tnr_round_up(int a, int b) { return tnr_cdiv(a, b) * b; }
 
+// The fixed-order fp64 sum of a 256-thread block (`sh`: 256 doubles of LDS); the result is valid in thread 0.  Every reduction of
+// the library ends in it: two runs add in the same order and are bit-identical.
+__device__ __forceinline__ double tnr_block_sum256(double v, double *sh) {
+    const int tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
 __device__ __forceinline__ float tnr_act(float v, int act, float slope) {
     if (act == TNR_ACT_LRELU) return v > 0.f ? v : v * slope;
     if (act == TNR_ACT_RELU) return v > 0.f ? v : 0.f;

@@ -17,7 +17,7 @@
 // The clamp mask comes from the saved output, not from the input: the backward then reads g and o (no second stencil).  torch's clamp
 // passes the gradient on the closed interval; an output of exactly 0 or 1 cannot tell "on the edge" from "beyond it", so it passes
 // nothing here.  The two differ only where x - L x is exactly -1 or +1.
-#include "common.h"
+#include "image_tile.h"
 
 namespace {
 
@@ -33,30 +33,28 @@ constexpr int TST = 64;                                  // horizontally filtere
 
 enum { LOW = 0, HIGH = 1, HIGH_B = 2 };
 
-struct ImView {                                          // an N x C x H x W batch in either dense layout
-    int64_t sN, sC, sH, sW;
-    int N, C, H, W;
-};
 struct Taps {
     float w[K];
 };
-
-ImView make_view(int N, int C, int H, int W, int layout) {
-    ImView v;
-    v.sN = (int64_t)C * H * W;
-    if (layout == 0) {
-        v.sC = (int64_t)H * W; v.sH = W; v.sW = 1;
-    } else {
-        v.sC = 1; v.sH = (int64_t)W * C; v.sW = C;
-    }
-    v.N = N; v.C = C; v.H = H; v.W = W;
-    return v;
-}
 
 // torch.clamp(v, 0, 1): a NaN stays a NaN (fminf / fmaxf would turn it into a bound)
 __device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
 
 __device__ __forceinline__ float masked_half(float g, float o) { return (o > 0.f && o < 1.f) ? 0.5f * g : 0.f; }
+__device__ __forceinline__ f32x4 masked_half(f32x4 g, f32x4 o) {
+    return f32x4{masked_half(g.x, o.x), masked_half(g.y, o.y), masked_half(g.z, o.z), masked_half(g.w, o.w)};
+}
+
+// what stage_tile stores: the source, or (HIGH_B) the gradient g' formed from it and the saved output
+template <int MODE>
+struct StagedPixel {
+    const float *src, *saved;
+    template <class V>
+    __device__ __forceinline__ void operator()(int64_t a, V (&v)[1]) const {
+        v[0] = *(const V *)(src + a);
+        if (MODE == HIGH_B) v[0] = masked_half(v[0], *(const V *)(saved + a));
+    }
+};
 
 // src: x (LOW, HIGH) or the incoming gradient g (LOW as a backward, HIGH_B); saved: the forward's output o (HIGH_B only)
 template <int MODE>
@@ -66,43 +64,13 @@ __global__ __launch_bounds__(256) void freqsep_kernel(const float *__restrict__ 
     __shared__ __attribute__((aligned(16))) float sS[IH * SST];
     __shared__ __attribute__((aligned(16))) float sT[IH * TST];
     const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tx = b % tilesX; b /= tilesX;
-    const int ty = b % tilesY; b /= tilesY;
-    const int c = b % g.C, n = b / g.C;
-    const int y0 = ty * TH, x0 = tx * TW;
+    int n, c, y0, x0;
+    tile_of_block<TW, TH>(g, tilesX, tilesY, &n, &c, &y0, &x0);
     const int64_t base = (int64_t)n * g.sN + (int64_t)c * g.sC;
-    if (vec) {
-        // NCHW, W a multiple of 4, 16-byte aligned operands: the 18 aligned groups of four columns x0 - 4 .. x0 + 67 of every staged
-        // row, each wholly inside or wholly outside the image; group gq is LDS columns 4 gq .. 4 gq + 3
-        constexpr int NG = IW / 4;
-        for (int i = tid; i < IH * NG; i += 256) {
-            const int r = i / NG, gq = i - r * NG;
-            const int yy = y0 - R + r, xg = x0 - R + 4 * gq;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};              // zero padding
-            if (yy >= 0 && yy < g.H && xg >= 0 && xg < g.W) {
-                const int64_t a = base + (int64_t)yy * g.sH + xg;
-                v = *(const f32x4 *)(src + a);
-                if (MODE == HIGH_B) {
-                    const f32x4 o = *(const f32x4 *)(saved + a);
-                    v.x = masked_half(v.x, o.x); v.y = masked_half(v.y, o.y); v.z = masked_half(v.z, o.z); v.w = masked_half(v.w, o.w);
-                }
-            }
-            *(f32x4 *)(sS + r * SST + 4 * gq) = v;
-        }
-    } else {
-        for (int i = tid; i < IH * IW; i += 256) {
-            const int r = i / IW, q = i - r * IW;
-            const int yy = y0 - R + r, xx = x0 - R + q;
-            float v = 0.f;                               // zero padding
-            if (yy >= 0 && yy < g.H && xx >= 0 && xx < g.W) {
-                const int64_t a = base + (int64_t)yy * g.sH + (int64_t)xx * g.sW;
-                v = src[a];
-                if (MODE == HIGH_B) v = masked_half(v, saved[a]);
-            }
-            sS[r * SST + q] = v;
-        }
-    }
+    // with 16-byte loads: the 18 aligned groups of four columns x0 - 4 .. x0 + 67 of every staged row; group gq is LDS columns
+    // 4 gq .. 4 gq + 3, one aligned 16-byte store
+    float *const tile[1] = {sS};
+    stage_tile<IH, IW, R, SST, R, IW>(g, base, y0, x0, vec, tile, StagedPixel<MODE>{src, saved});
     __syncthreads();
     // horizontal pass: 24 rows x 16 groups of four columns; output column j of the tile is centred on staged column j + 4
     for (int i = tid; i < IH * (TW / 4); i += 256) {
@@ -151,9 +119,9 @@ __global__ __launch_bounds__(256) void freqsep_kernel(const float *__restrict__ 
         for (int j = 0; j < 4; ++j) e[j] = mul * e[j];
     }
     const int yy = y0 + row;
-    if (yy >= g.H) return;
+    if (yy >= g.h) return;
     if (vec) {
-        if (x0 + col >= g.W) return;                     // the thread's four columns are one aligned group inside the image
+        if (x0 + col >= g.w) return;                     // the thread's four columns are one aligned group inside the image
         f32x4 *o = (f32x4 *)(out + base + (int64_t)yy * g.sH + x0 + col);
         f32x4 r = {e[0], e[1], e[2], e[3]};
         if (MODE != HIGH && accumulate) r = *o + r;
@@ -162,31 +130,25 @@ __global__ __launch_bounds__(256) void freqsep_kernel(const float *__restrict__ 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int xx = x0 + col + j;
-            if (xx >= g.W) continue;
+            if (xx >= g.w) continue;
             const int64_t a = base + (int64_t)yy * g.sH + (int64_t)xx * g.sW;
             out[a] = (MODE != HIGH && accumulate) ? out[a] + e[j] : e[j];
         }
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int MODE>
 int launch(const char *what, const float *src, const float *saved, int N, int C, int H, int W, int layout, const float *taps9, float *out,
            const float *gscale, int accumulate, void *stream) {
-    TNR_REQUIRE(N > 0 && C >= 1 && H > 0 && W > 0, "%s: bad shape %d x %d x %d x %d", what, N, C, H, W);
-    TNR_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (NCHW) or 1 (channels-last)", what);
+    int64_t blocks;
+    int tilesX, tilesY;
+    if (int rc = check_batch(what, N, C, H, W, layout, TW, TH, &blocks, &tilesX, &tilesY)) return rc;
     TNR_REQUIRE(src && out && taps9 && src != out, "%s: null or aliased pointer", what);
     TNR_REQUIRE(MODE != HIGH_B || (saved && saved != out), "%s: the saved forward output is missing or aliases the result", what);
-    const int tilesY = tnr_cdiv(H, TH), tilesX = tnr_cdiv(W, TW);
-    const int64_t blocks = (int64_t)N * C * tilesY * tilesX;
-    TNR_REQUIRE(blocks < (1ll << 31), "%s: batch too large", what);
     Taps t;
     for (int k = 0; k < K; ++k) t.w[k] = taps9[k];
-    // 16-byte loads / stores: NCHW rows that start on a 16-byte boundary and split into whole groups of four
-    const int vec = layout == 0 && (W & 3) == 0 && aligned16(src) && aligned16(out) && (!saved || aligned16(saved));
     hipLaunchKernelGGL(freqsep_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, saved,
-                       make_view(N, C, H, W, layout), t, tilesX, tilesY, out, gscale, accumulate, vec);
+                       make_view(N, C, H, W, layout), t, tilesX, tilesY, out, gscale, accumulate, vec_rows(layout, W, src, out, saved));
     return tnr_check_launch(what);
 }
 

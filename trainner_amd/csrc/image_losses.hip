@@ -13,7 +13,7 @@
 //   sum_kernel         the blocks' partials in a fixed order -> loss = scale * sum
 //
 // All reductions are fixed-order (one fp64 slot per block, then one block): two runs are bit-identical.  No float atomics.
-#include "common.h"
+#include "image_tile.h"
 
 namespace {
 
@@ -25,25 +25,9 @@ constexpr int FIW = TW + 2 * FR, FIH = TH + 2 * FR;      // 78 x 30 staged diffe
 constexpr int FST = 81;                                  // LDS row stride: = 1 mod 4, so the 4 rows of a wave start on banks 0, 1, 2, 3
 constexpr int DST = TW + 3;                              // finite-difference tiles: 66 columns staged, stride 67
 
-struct ImView {                                          // an N x C x H x W batch in either dense layout
-    int64_t sN, sC, sH, sW;
-    int N, C, H, W;
-};
 struct FilterTaps {
     float w[FK * FK];
 };
-
-ImView make_view(int N, int C, int H, int W, int layout) {
-    ImView v;
-    v.sN = (int64_t)C * H * W;
-    if (layout == 0) {
-        v.sC = (int64_t)H * W; v.sH = W; v.sW = 1;
-    } else {
-        v.sC = 1; v.sH = (int64_t)W * C; v.sW = C;
-    }
-    v.N = N; v.C = C; v.H = H; v.W = W;
-    return v;
-}
 
 __device__ __forceinline__ float sgn(float e) { return e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f); }
 
@@ -69,35 +53,23 @@ __device__ __forceinline__ float drho(float e, int crit) {
     }
 }
 
-__device__ __forceinline__ double il_block_sum(double v, double *sh) {      // 256 threads, fixed order; valid in thread 0
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(256) void sum_kernel(const double *__restrict__ partial, int64_t count, double scale, float *__restrict__ loss) {
     __shared__ double sh[256];
-    double acc = 0;
-    for (int64_t i = threadIdx.x; i < count; i += 256) acc += partial[i];
-    acc = il_block_sum(acc, sh);
+    double acc;
+    sum_partials<1>(partial, count, sh, &acc);
     if (threadIdx.x == 0) *loss = (float)(acc * scale);
 }
 
-__device__ __forceinline__ void tile_of_block(const ImView &g, int tilesX, int tilesY, int *n, int *c, int *y0, int *x0) {
-    int b = blockIdx.x;
-    const int tx = b % tilesX; b /= tilesX;
-    const int ty = b % tilesY; b /= tilesY;
-    *c = b % g.C; *n = b / g.C;
-    *y0 = ty * TH; *x0 = tx * TW;
-}
+// what stage_tile stores for the filter: the difference x - y, or (BWD) the rho'(e) map
+template <int BWD>
+struct DiffPixel {
+    const float *x, *y;
+    template <class V>
+    __device__ __forceinline__ void operator()(int64_t a, V (&v)[1]) const {
+        v[0] = *(const V *)(x + a);
+        if (!BWD) v[0] -= *(const V *)(y + a);
+    }
+};
 
 // BWD = 0: src = x, y != nullptr, e = L * (x - y); partial[block] = sum rho(e); dmap (nullable) = rho'(e).
 // BWD = 1: src = the rho'(e) map, out = (accumulate ? out : 0) + mul * (L * src) with the taps already flipped by the host.
@@ -110,38 +82,12 @@ __global__ __launch_bounds__(256) void filter_kernel(const float *__restrict__ s
     __shared__ double sh[256];
     const int tid = threadIdx.x;
     int n, c, y0, x0;
-    tile_of_block(g, tilesX, tilesY, &n, &c, &y0, &x0);
+    tile_of_block<TW, TH>(g, tilesX, tilesY, &n, &c, &y0, &x0);
     const int64_t base = (int64_t)n * g.sN + (int64_t)c * g.sC;
-    if (vec) {
-        // NCHW, W a multiple of 4, 16-byte aligned operands: the 20 aligned groups of four columns x0 - 8 .. x0 + 71 of every staged
-        // row, each wholly inside or wholly outside the image.  Group gq lands on LDS columns 4 gq - 1 .. 4 gq + 2; column -1 is
-        // dropped, column 78 falls into the row's padding (FST = 81)
-        constexpr int FG = (TW + 16) / 4;
-        for (int i = tid; i < FIH * FG; i += 256) {
-            const int r = i / FG, gq = i - r * FG;
-            const int yy = y0 - FR + r, xg = x0 - 8 + 4 * gq;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};              // zero padding
-            if (yy >= 0 && yy < g.H && xg >= 0 && xg < g.W) {
-                const int64_t a = base + (int64_t)yy * g.sH + xg;
-                v = *(const f32x4 *)(src + a);
-                if (!BWD) v -= *(const f32x4 *)(y + a);
-            }
-            float *d = sD + r * FST + 4 * gq - 1;
-            if (gq > 0) d[0] = v.x;
-            d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-    } else {
-        for (int i = tid; i < FIH * FIW; i += 256) {
-            const int r = i / FIW, q = i - r * FIW;
-            const int yy = y0 - FR + r, xx = x0 - FR + q;
-            float v = 0.f;                               // zero padding
-            if (yy >= 0 && yy < g.H && xx >= 0 && xx < g.W) {
-                const int64_t a = base + (int64_t)yy * g.sH + (int64_t)xx * g.sW;
-                v = BWD ? src[a] : src[a] - y[a];
-            }
-            sD[r * FST + q] = v;
-        }
-    }
+    // with 16-byte loads: the 20 aligned groups of four columns x0 - 8 .. x0 + 71 of every staged row.  Group gq lands on LDS columns
+    // 4 gq - 1 .. 4 gq + 2; column -1 is dropped, column 78 falls into the row's padding (FST = 81)
+    float *const tile[1] = {sD};
+    stage_tile<FIH, FIW, FR, FST, 8, FIW + 1>(g, base, y0, x0, vec, tile, DiffPixel<BWD>{src, y});
     __syncthreads();
     const int row = tid >> 4, col = (tid & 15) * 4;
     float e0 = 0.f, e1 = 0.f, e2 = 0.f, e3 = 0.f;
@@ -164,7 +110,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const float *__restrict__ s
     double acc = 0;
     float mul = 0.f;
     if (BWD) mul = scale * (gscale ? *gscale : 1.f);
-    if (vec && yy < g.H && x0 + col < g.W) {             // the thread's four columns are one aligned group inside the image
+    if (vec && yy < g.h && x0 + col < g.w) {             // the thread's four columns are one aligned group inside the image
         f32x4 *o = out ? (f32x4 *)(out + base + (int64_t)yy * g.sH + x0 + col) : nullptr;
         f32x4 r;
         if (BWD) {
@@ -182,7 +128,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const float *__restrict__ s
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int xx = x0 + col + j;
-            if (yy >= g.H || xx >= g.W) continue;
+            if (yy >= g.h || xx >= g.w) continue;
             const int64_t a = base + (int64_t)yy * g.sH + (int64_t)xx * g.sW;
             if (BWD) {
                 const float gv = mul * e[j];
@@ -194,7 +140,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const float *__restrict__ s
         }
     }
     if (!BWD) {
-        acc = il_block_sum(acc, sh);
+        acc = tnr_block_sum256(acc, sh);
         if (tid == 0) partial[blockIdx.x] = acc;
     }
 }
@@ -215,46 +161,24 @@ __device__ __forceinline__ Fd4 fd_resp(const float *s, int st, int i, int j, int
     return r;
 }
 
-// stages rows y0 - up .. y0 + TH and columns x0 - up .. x0 + TW of x (and y, when given) with zeros outside the image
+// what stage_tile stores for the finite differences: x and y (zeros when there is no y) in two tiles
+struct PairPixel {
+    const float *x, *y;
+    template <class V>
+    __device__ __forceinline__ void operator()(int64_t a, V (&v)[2]) const {
+        v[0] = *(const V *)(x + a);
+        if (y) v[1] = *(const V *)(y + a);
+    }
+};
+
+// stages rows y0 - UP .. y0 + TH and columns x0 - UP .. x0 + TW of x and of y.  With 16-byte loads: the 18 aligned groups of four
+// columns x0 - 4 .. x0 + 67 of every staged row; element k of group gq is staged column 4 gq - 4 + UP + k, kept when it is one of the
+// TW + 1 + UP columns the tile holds
+template <int UP>
 __device__ __forceinline__ void fd_stage(const float *__restrict__ x, const float *__restrict__ y, const ImView &g, int64_t base, int y0, int x0,
-                                         int up, int vec, float *sX, float *sY) {
-    const int ih = TH + 1 + up, iw = TW + 1 + up;
-    if (vec) {
-        // NCHW, W a multiple of 4, 16-byte aligned operands: the 18 aligned groups of four columns x0 - 4 .. x0 + 67 of every staged
-        // row; element k of group gq is staged column 4 gq - 4 + up + k, kept when it is one of the iw columns the tile holds
-        constexpr int DG = (TW + 8) / 4;
-        for (int i = threadIdx.x; i < ih * DG; i += 256) {
-            const int r = i / DG, gq = i - r * DG;
-            const int yy = y0 - up + r, xg = x0 - 4 + 4 * gq;
-            f32x4 vx = {0.f, 0.f, 0.f, 0.f}, vy = {0.f, 0.f, 0.f, 0.f};
-            if (yy >= 0 && yy < g.H && xg >= 0 && xg < g.W) {
-                const int64_t a = base + (int64_t)yy * g.sH + xg;
-                vx = *(const f32x4 *)(x + a);
-                if (y) vy = *(const f32x4 *)(y + a);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int q = 4 * gq - 4 + up + k;
-                if (q >= 0 && q < iw) {
-                    sX[r * DST + q] = vx[k];
-                    sY[r * DST + q] = vy[k];
-                }
-            }
-        }
-        return;
-    }
-    for (int i = threadIdx.x; i < ih * iw; i += 256) {
-        const int r = i / iw, q = i - r * iw;
-        const int yy = y0 - up + r, xx = x0 - up + q;
-        float vx = 0.f, vy = 0.f;
-        if (yy >= 0 && yy < g.H && xx >= 0 && xx < g.W) {
-            const int64_t a = base + (int64_t)yy * g.sH + (int64_t)xx * g.sW;
-            vx = x[a];
-            if (y) vy = y[a];
-        }
-        sX[r * DST + q] = vx;
-        sY[r * DST + q] = vy;
-    }
+                                         int vec, float *sX, float *sY) {
+    float *const tiles[2] = {sX, sY};
+    stage_tile<TH + 1 + UP, TW + 1 + UP, UP, DST, 4, TW + 1 + UP>(g, base, y0, x0, vec, tiles, PairPixel{x, y});
 }
 
 // the responses' differences e = dir(x) - dir(y) at (i, j); s indexes the staged tiles at that pixel
@@ -271,20 +195,20 @@ __global__ __launch_bounds__(256) void fd_fwd_kernel(const float *__restrict__ x
     __shared__ double sh[256];
     const int tid = threadIdx.x;
     int n, c, y0, x0;
-    tile_of_block(g, tilesX, tilesY, &n, &c, &y0, &x0);
-    fd_stage(x, y, g, (int64_t)n * g.sN + (int64_t)c * g.sC, y0, x0, 0, vec, sX, sY);
+    tile_of_block<TW, TH>(g, tilesX, tilesY, &n, &c, &y0, &x0);
+    fd_stage<0>(x, y, g, (int64_t)n * g.sN + (int64_t)c * g.sC, y0, x0, vec, sX, sY);
     __syncthreads();
     double acc = 0;
     for (int i = tid; i < TH * TW; i += 256) {
         const int r = i / TW, q = i % TW;
         const int yy = y0 + r, xx = x0 + q;
-        if (yy >= g.H || xx >= g.W) continue;
-        const Fd4 e = fd_err(sX, sY, r * DST + q, yy, xx, g.H, g.W);
+        if (yy >= g.h || xx >= g.w) continue;
+        const Fd4 e = fd_err(sX, sY, r * DST + q, yy, xx, g.h, g.w);
         float v = rho(e.dx, crit) + rho(e.dy, crit);     // zeroed responses still count rho(0) (cb: 1e-6 each)
         if (dirs == 4) v += rho(e.dp, crit) + rho(e.dn, crit);
         acc += (double)v;
     }
-    acc = il_block_sum(acc, sh);
+    acc = tnr_block_sum256(acc, sh);
     if (tid == 0) partial[blockIdx.x] = acc;
 }
 
@@ -294,12 +218,12 @@ __global__ __launch_bounds__(256) void fd_bwd_kernel(const float *__restrict__ x
     __shared__ float sX[(TH + 2) * DST], sY[(TH + 2) * DST];
     const int tid = threadIdx.x;
     int n, c, y0, x0;
-    tile_of_block(g, tilesX, tilesY, &n, &c, &y0, &x0);
+    tile_of_block<TW, TH>(g, tilesX, tilesY, &n, &c, &y0, &x0);
     const int64_t base = (int64_t)n * g.sN + (int64_t)c * g.sC;
-    fd_stage(x, y, g, base, y0, x0, 1, vec, sX, sY);
+    fd_stage<1>(x, y, g, base, y0, x0, vec, sX, sY);
     __syncthreads();
     const float mul = scale * (gscale ? *gscale : 1.f);
-    const int H = g.H, W = g.W;
+    const int H = g.h, W = g.w;
     for (int t = tid; t < TH * TW; t += 256) {
         const int r = t / TW, q = t % TW;
         const int i = y0 + r, j = x0 + q;
@@ -350,7 +274,7 @@ __global__ __launch_bounds__(256) void point_fwd_kernel(const float *__restrict_
     } else {
         for (int64_t i = t0; i < n; i += step) acc += (double)rho(a[i] - b[i], crit);
     }
-    acc = il_block_sum(acc, sh);
+    acc = tnr_block_sum256(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -377,14 +301,8 @@ __global__ __launch_bounds__(256) void point_bwd_kernel(const float *__restrict_
     }
 }
 
-int check_batch(const char *what, int N, int C, int H, int W, int layout, int crit, int64_t *blocks, int *tilesX, int *tilesY) {
-    TNR_REQUIRE(N > 0 && C >= 1 && H > 0 && W > 0, "%s: bad shape %d x %d x %d x %d", what, N, C, H, W);
-    TNR_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (NCHW) or 1 (channels-last)", what);
+int check_crit(const char *what, int crit) {
     TNR_REQUIRE(crit >= CRIT_L1 && crit <= CRIT_CLIPL1, "%s: unknown criterion %d", what, crit);
-    *tilesY = tnr_cdiv(H, TH);
-    *tilesX = tnr_cdiv(W, TW);
-    *blocks = (int64_t)N * C * *tilesY * *tilesX;
-    TNR_REQUIRE(*blocks < (1ll << 31), "%s: batch too large", what);
     return TNR_OK;
 }
 
@@ -396,13 +314,6 @@ int make_taps(const char *what, const float *taps, int K, int flip, FilterTaps *
     for (int r = 0; r < K; ++r)
         for (int q = 0; q < K; ++q) t->w[(o + r) * FK + o + q] = flip ? taps[(K - 1 - r) * K + (K - 1 - q)] : taps[r * K + q];
     return TNR_OK;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-// 16-byte loads / stores in the stencil kernels: NCHW rows that start on a 16-byte boundary and split into whole groups of four
-int vec_rows(int layout, int W, const void *a, const void *b, const void *c) {
-    return layout == 0 && (W & 3) == 0 && aligned16(a) && (!b || aligned16(b)) && (!c || aligned16(c));
 }
 
 }  // namespace
@@ -417,7 +328,8 @@ extern "C" int tnr_filter_loss_fwd(const float *x, const float *y, int32_t N, in
                                    int64_t ws_bytes, void *stream) {
     int64_t blocks;
     int tilesX, tilesY;
-    if (int rc = check_batch("filter_loss_fwd", N, C, H, W, layout, crit, &blocks, &tilesX, &tilesY)) return rc;
+    if (int rc = check_batch("filter_loss_fwd", N, C, H, W, layout, TW, TH, &blocks, &tilesX, &tilesY)) return rc;
+    if (int rc = check_crit("filter_loss_fwd", crit)) return rc;
     TNR_REQUIRE(x && y && loss, "filter_loss_fwd: null pointer");
     TNR_REQUIRE(ws && ws_bytes >= tnr_imgloss_workspace_bytes(N, C, H, W), "filter_loss_fwd: workspace missing or too small");
     FilterTaps t;
@@ -433,7 +345,7 @@ extern "C" int tnr_filter_loss_bwd(const float *dmap, int32_t N, int32_t C, int3
                                    double scale, const float *gscale, float *gx, int32_t accumulate, void *stream) {
     int64_t blocks;
     int tilesX, tilesY;
-    if (int rc = check_batch("filter_loss_bwd", N, C, H, W, layout, CRIT_L1, &blocks, &tilesX, &tilesY)) return rc;
+    if (int rc = check_batch("filter_loss_bwd", N, C, H, W, layout, TW, TH, &blocks, &tilesX, &tilesY)) return rc;
     TNR_REQUIRE(dmap && gx && dmap != gx, "filter_loss_bwd: null or aliased pointer");
     FilterTaps t;
     if (int rc = make_taps("filter_loss_bwd", taps, K, 1, &t)) return rc;
@@ -447,7 +359,8 @@ extern "C" int tnr_fd_loss_fwd(const float *x, const float *y, int32_t N, int32_
                                int32_t crit, double scale, float *loss, void *ws, int64_t ws_bytes, void *stream) {
     int64_t blocks;
     int tilesX, tilesY;
-    if (int rc = check_batch("fd_loss_fwd", N, C, H, W, layout, crit, &blocks, &tilesX, &tilesY)) return rc;
+    if (int rc = check_batch("fd_loss_fwd", N, C, H, W, layout, TW, TH, &blocks, &tilesX, &tilesY)) return rc;
+    if (int rc = check_crit("fd_loss_fwd", crit)) return rc;
     TNR_REQUIRE(x && loss && (dirs == 2 || dirs == 4), "fd_loss_fwd: null pointer or dirs not 2 / 4");
     TNR_REQUIRE(ws && ws_bytes >= tnr_imgloss_workspace_bytes(N, C, H, W), "fd_loss_fwd: workspace missing or too small");
     hipStream_t s = (hipStream_t)stream;
@@ -461,7 +374,8 @@ extern "C" int tnr_fd_loss_bwd(const float *x, const float *y, int32_t N, int32_
                                int32_t crit, double scale, const float *gscale, float *gx, int32_t accumulate, void *stream) {
     int64_t blocks;
     int tilesX, tilesY;
-    if (int rc = check_batch("fd_loss_bwd", N, C, H, W, layout, crit, &blocks, &tilesX, &tilesY)) return rc;
+    if (int rc = check_batch("fd_loss_bwd", N, C, H, W, layout, TW, TH, &blocks, &tilesX, &tilesY)) return rc;
+    if (int rc = check_crit("fd_loss_bwd", crit)) return rc;
     TNR_REQUIRE(x && gx && x != gx && (dirs == 2 || dirs == 4), "fd_loss_bwd: null or aliased pointer, or dirs not 2 / 4");
     hipLaunchKernelGGL(fd_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, y, make_view(N, C, H, W, layout), (int)dirs,
                        (int)crit, tilesX, tilesY, (float)scale, gscale, gx, (int)accumulate, vec_rows(layout, W, x, y, nullptr));
@@ -471,7 +385,7 @@ extern "C" int tnr_fd_loss_bwd(const float *x, const float *y, int32_t N, int32_
 extern "C" int tnr_pointwise_loss_fwd(const float *a, const float *b, int64_t n, int32_t crit, double scale, float *loss, void *ws,
                                       void *stream) {
     TNR_REQUIRE(a && b && loss && ws && n > 0, "pointwise_loss_fwd: bad arguments");
-    TNR_REQUIRE(crit >= CRIT_L1 && crit <= CRIT_CLIPL1, "pointwise_loss_fwd: unknown criterion %d", crit);
+    if (int rc = check_crit("pointwise_loss_fwd", crit)) return rc;
     const int vec = aligned16(a) && aligned16(b);
     int64_t nb = tnr_cdiv64(vec ? tnr_cdiv64(n, 4) : n, 256);
     if (nb > PT_BLOCKS) nb = PT_BLOCKS;
@@ -484,7 +398,7 @@ extern "C" int tnr_pointwise_loss_fwd(const float *a, const float *b, int64_t n,
 extern "C" int tnr_pointwise_loss_bwd(const float *a, const float *b, int64_t n, int32_t crit, double scale, const float *gscale, float *ga,
                                       int32_t accumulate, void *stream) {
     TNR_REQUIRE(a && b && ga && n > 0, "pointwise_loss_bwd: bad arguments");
-    TNR_REQUIRE(crit >= CRIT_L1 && crit <= CRIT_CLIPL1, "pointwise_loss_bwd: unknown criterion %d", crit);
+    if (int rc = check_crit("pointwise_loss_bwd", crit)) return rc;
     const int vec = aligned16(a) && aligned16(b) && aligned16(ga);
     int64_t nb = tnr_cdiv64(vec ? tnr_cdiv64(n, 4) : n, 256);
     if (nb > 4096) nb = 4096;

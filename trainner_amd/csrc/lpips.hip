@@ -144,14 +144,10 @@ __global__ void __launch_bounds__(HEAD_BLOCK) lpips_head_kernel(const float *f0,
         }
         acc += group_sum(d);                                   // every lane of the group holds the pixel's value
     }
-    red[threadIdx.x] = lane == 0 ? acc : 0.0;
-    __syncthreads();
-    for (int s = HEAD_BLOCK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
+    static_assert(HEAD_BLOCK == 256, "tnr_block_sum256 adds 256 slots");
+    acc = tnr_block_sum256(lane == 0 ? acc : 0.0, red);
     if (threadIdx.x == 0) {
-        ws[((int64_t)layer * N + n) * HEAD_MAX_BLOCKS + blockIdx.x] = red[0];
+        ws[((int64_t)layer * N + n) * HEAD_MAX_BLOCKS + blockIdx.x] = acc;
         if (blockIdx.x == 0 && n == 0) {
             double *meta = ws + (int64_t)L * N * HEAD_MAX_BLOCKS;
             meta[2 * layer] = (double)HW;

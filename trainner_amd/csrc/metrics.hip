@@ -29,18 +29,6 @@ __global__ void tensor2np_u8_kernel(const float *src, int N, int C, int H, int W
     }
 }
 
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // blockIdx.y = image; partial[(n * MT_BLOCKS + blockIdx.x) * 2 + {0: squared error, 1: ssim sum}]
 __global__ void __launch_bounds__(256) psnr_ssim_partial_kernel(const uint8_t *a, const uint8_t *b, int H, int W, int C, int crop,
                                                                  int want_ssim, double *partial) {
@@ -67,7 +55,7 @@ __global__ void __launch_bounds__(256) psnr_ssim_partial_kernel(const uint8_t *a
         const int d = (int)pa[o] - (int)pb[o];
         se += (double)(d * d);
     }
-    se = block_sum(se, sh);
+    se = tnr_block_sum256(se, sh);
     double ss = 0.0;
     if (want_ssim && h >= 11 && w >= 11) {
         const double C1 = (0.01 * 255) * (0.01 * 255), C2 = (0.03 * 255) * (0.03 * 255);
@@ -91,7 +79,7 @@ __global__ void __launch_bounds__(256) psnr_ssim_partial_kernel(const uint8_t *a
             const double m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
             ss += ((2 * m12 + C1) * (2 * (s12 - m12) + C2)) / ((m11 + m22 + C1) * ((s11 - m11) + (s22 - m22) + C2));
         }
-        ss = block_sum(ss, sh);
+        ss = tnr_block_sum256(ss, sh);
     }
     if (threadIdx.x == 0) {
         partial[((size_t)n * MT_BLOCKS + blockIdx.x) * 2 + 0] = se;

@@ -8,21 +8,6 @@ namespace {
 
 constexpr int RED_BLOCKS = 512;  // max partial slabs of any reduction below
 
-__device__ __forceinline__ double block_reduce_sum(double v, double *sh) {
-    // 256 threads; result valid in thread 0
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // ---------------------------------------------------------------------------------- BatchNorm
 // partial[b][c] = {sum f(z), sum g(z)} over the block's pixel range, per channel.
 // MODE 0 (fwd):  f = z,            g = z*z
@@ -308,7 +293,7 @@ __global__ void linear_fwd_kernel(const float *x, const float *w, const float *b
     const float *xr = x + (size_t)n * In, *wr = w + (size_t)o * In;
     float acc = 0.f;
     for (int i = threadIdx.x; i < In; i += 256) acc += xr[i] * wr[i];
-    const double tot = block_reduce_sum((double)acc, sh);
+    const double tot = tnr_block_sum256((double)acc, sh);
     if (threadIdx.x == 0) y[(size_t)n * Out + o] = tnr_act((float)tot + (b ? b[o] : 0.f), act, slope);
 }
 
@@ -349,7 +334,7 @@ __global__ void l1_partial_kernel(const float *a, const float *b, int64_t n, dou
     double acc = 0;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
         acc += (double)fabsf(a[e] - b[e]);
-    const double tot = block_reduce_sum(acc, sh);
+    const double tot = tnr_block_sum256(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -381,8 +366,8 @@ __global__ void ragan_a_kernel(const float *pf, const float *pr, int n, float *s
         sf += pf[i];
         sr += pr[i];
     }
-    sf = block_reduce_sum(sf, sh);
-    sr = block_reduce_sum(sr, sh);
+    sf = tnr_block_sum256(sf, sh);
+    sr = tnr_block_sum256(sr, sh);
     if (threadIdx.x == 0) {
         sums[0] = (float)sf;
         sums[1] = (float)sr;
@@ -408,10 +393,10 @@ __global__ void ragan_b_kernel(const float *pf, const float *pr, int n, int stag
             sb += sigmoidf(df);
         }
     }
-    t1 = block_reduce_sum(t1, sh);
-    t2 = block_reduce_sum(t2, sh);
-    sa = block_reduce_sum(sa, sh);
-    sb = block_reduce_sum(sb, sh);
+    t1 = tnr_block_sum256(t1, sh);
+    t2 = tnr_block_sum256(t2, sh);
+    sa = tnr_block_sum256(sa, sh);
+    sb = tnr_block_sum256(sb, sh);
     __syncthreads();
     if (threadIdx.x == 0) {
         sums[3] = (float)t1;
@@ -434,8 +419,8 @@ __global__ void ragan_a_partial_kernel(const float *pf, const float *pr, int n, 
         sf += pf[i];
         sr += pr[i];
     }
-    sf = block_reduce_sum(sf, sh);
-    sr = block_reduce_sum(sr, sh);
+    sf = tnr_block_sum256(sf, sh);
+    sr = tnr_block_sum256(sr, sh);
     if (threadIdx.x == 0) {
         ws[2 * blockIdx.x] = sf;
         ws[2 * blockIdx.x + 1] = sr;
@@ -473,10 +458,10 @@ __global__ void ragan_b_partial_kernel(const float *pf, const float *pr, int n, 
             sb += sigmoidf(df);
         }
     }
-    t1 = block_reduce_sum(t1, sh);
-    t2 = block_reduce_sum(t2, sh);
-    sa = block_reduce_sum(sa, sh);
-    sb = block_reduce_sum(sb, sh);
+    t1 = tnr_block_sum256(t1, sh);
+    t2 = tnr_block_sum256(t2, sh);
+    sa = tnr_block_sum256(sa, sh);
+    sb = tnr_block_sum256(sb, sh);
     if (threadIdx.x == 0) {
         double *w = ws + 4 * blockIdx.x;
         w[0] = t1; w[1] = t2; w[2] = sa; w[3] = sb;
@@ -560,7 +545,7 @@ __global__ void sumsq_partial_kernel(const float *g, int64_t n, double *partial)
     double acc = 0;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
         acc += (double)g[e] * (double)g[e];
-    const double tot = block_reduce_sum(acc, sh);
+    const double tot = tnr_block_sum256(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 

@@ -11,17 +11,13 @@
 //   combine_kernel       relu, powers, product over levels, batch mean; the per-image scalars the backward launches read
 //
 // All reductions are fixed-order (per-block slots, then one block per image): a step is reproducible run to run.  No float atomics.
-#include "common.h"
+#include "image_tile.h"
 
 namespace {
 
 constexpr int SS_KMAX = 11;      // window taps (odd, <= 11)
 constexpr int SS_MAXLEV = 8;     // MS-SSIM levels
 
-struct SsView {                  // the (shaved) h x w region of an N x C x H x W batch in either dense layout
-    int64_t sN, sC, sH, sW, off;
-    int N, C, h, w;
-};
 struct SsWin {
     float w[SS_KMAX];
     int K;
@@ -31,32 +27,6 @@ struct SsLevels {
     double expo[SS_MAXLEV];      // exponent of the level's factor
     int levels;
 };
-
-SsView make_view(int N, int C, int H, int W, int layout, int shave) {
-    SsView v;
-    if (layout == 0) {
-        v.sN = (int64_t)C * H * W; v.sC = (int64_t)H * W; v.sH = W; v.sW = 1;
-    } else {
-        v.sN = (int64_t)C * H * W; v.sC = 1; v.sH = (int64_t)W * C; v.sW = C;
-    }
-    v.off = (int64_t)shave * v.sH + (int64_t)shave * v.sW;
-    v.N = N; v.C = C; v.h = H - 2 * shave; v.w = W - 2 * shave;
-    return v;
-}
-
-__device__ __forceinline__ double ss_block_sum(double v, double *sh) {      // 256 threads, fixed order; valid in thread 0
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // the five moments at one map position -> the two maps' values (ssim.py:160-186); s1neg: the sigma1_sq clamp acted
 struct SsPoint {
@@ -81,18 +51,15 @@ __device__ __forceinline__ SsPoint ss_point(float mu1, float mu2, float e11, flo
 constexpr int FT = 32;                                  // forward tile (FT x FT map positions)
 constexpr int FI = FT + SS_KMAX - 1;
 
-__global__ __launch_bounds__(256) void ssim_fwd_kernel(const float *__restrict__ X, const float *__restrict__ Y, SsView g, SsWin win,
+__global__ __launch_bounds__(256) void ssim_fwd_kernel(const float *__restrict__ X, const float *__restrict__ Y, ImView g, SsWin win,
                                                        float C1, float C2, int tilesX, int tilesY, double *__restrict__ partial) {
     __shared__ float sX[FI * FI], sY[FI * FI];
     __shared__ float sR[5][FI * FT];
     __shared__ double sh[256];
     const int K = win.K, tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tx = b % tilesX; b /= tilesX;
-    const int ty = b % tilesY; b /= tilesY;
-    const int c = b % g.C, n = b / g.C;
+    int n, c, y0, x0;
+    tile_of_block<FT, FT>(g, tilesX, tilesY, &n, &c, &y0, &x0);
     const int oh = g.h - K + 1, ow = g.w - K + 1;
-    const int y0 = ty * FT, x0 = tx * FT;
     const int th = min(FT, oh - y0), tw = min(FT, ow - x0);
     const int ih = th + K - 1, iw = tw + K - 1;          // rows y0 .. y0+ih-1 <= h-1, columns likewise: all inside the region
     const int64_t base = g.off + (int64_t)n * g.sN + (int64_t)c * g.sC;
@@ -132,8 +99,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float *__restrict__
         as += (double)(p.lum * p.cs);
         ac += (double)p.cs;
     }
-    as = ss_block_sum(as, sh);
-    ac = ss_block_sum(ac, sh);
+    as = tnr_block_sum256(as, sh);
+    ac = tnr_block_sum256(ac, sh);
     if (tid == 0) {
         partial[(size_t)blockIdx.x * 2] = as;
         partial[(size_t)blockIdx.x * 2 + 1] = ac;
@@ -142,17 +109,11 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float *__restrict__
 
 __global__ __launch_bounds__(256) void ssim_sum_kernel(const double *__restrict__ partial, int per_image, double *__restrict__ sums) {
     __shared__ double sh[256];
-    const double *p = partial + (size_t)blockIdx.x * per_image * 2;
-    double as = 0, ac = 0;
-    for (int i = threadIdx.x; i < per_image; i += 256) {
-        as += p[2 * i];
-        ac += p[2 * i + 1];
-    }
-    as = ss_block_sum(as, sh);
-    ac = ss_block_sum(ac, sh);
+    double a[2];
+    sum_partials<2>(partial + (size_t)blockIdx.x * per_image * 2, per_image, sh, a);
     if (threadIdx.x == 0) {
-        sums[blockIdx.x * 2] = as;
-        sums[blockIdx.x * 2 + 1] = ac;
+        sums[blockIdx.x * 2] = a[0];
+        sums[blockIdx.x * 2 + 1] = a[1];
     }
 }
 
@@ -160,7 +121,7 @@ constexpr int BH = 16, BW = 32;                          // backward tile of gX
 constexpr int BCH = BH + SS_KMAX - 1, BCW = BW + SS_KMAX - 1;            // coefficient tile (one halo)
 constexpr int BIH = BH + 2 * SS_KMAX - 2, BIW = BW + 2 * SS_KMAX - 2;    // input tile (double halo)
 
-__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float *__restrict__ X, const float *__restrict__ Y, SsView g, SsWin win,
+__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float *__restrict__ X, const float *__restrict__ Y, ImView g, SsWin win,
                                                        float C1, float C2, const float *__restrict__ coef,
                                                        const float *__restrict__ gscale, float *__restrict__ gX, int accumulate,
                                                        int shave, int tilesX, int tilesY) {
@@ -168,13 +129,11 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float *__restrict__
     __shared__ float sR[5][BIH * BCW];                   // row-passed moments; later the row-passed coefficient maps
     __shared__ float sC[3][BCH * BCW];
     const int K = win.K, tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tx = b % tilesX; b /= tilesX;
-    const int ty = b % tilesY; b /= tilesY;
-    const int c = b % g.C, n = b / g.C;
+    int n, c, y0, x0;
+    tile_of_block<BW, BH>(g, tilesX, tilesY, &n, &c, &y0, &x0);
     const int oh = g.h - K + 1, ow = g.w - K + 1;
     const int H = g.h + 2 * shave, W = g.w + 2 * shave;
-    const int ry0 = ty * BH - shave, rx0 = tx * BW - shave;      // tile origin in region coordinates (may be negative)
+    const int ry0 = y0 - shave, rx0 = x0 - shave;                // tile origin in region coordinates (may be negative)
     const int iy0 = ry0 - (K - 1), ix0 = rx0 - (K - 1);          // origin of the input tile and of the coefficient tile
     const int ih = BH + 2 * K - 2, iw = BW + 2 * K - 2, ch = BH + K - 1, cw = BW + K - 1;
     const int64_t base = g.off + (int64_t)n * g.sN + (int64_t)c * g.sC;
@@ -247,7 +206,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float *__restrict__
     float *gplane = gX + (int64_t)n * g.sN + (int64_t)c * g.sC;
     for (int i = tid; i < BH * BW; i += 256) {           // column pass and the three terms of gX
         const int r = i / BW, col = i % BW;
-        const int fy = ty * BH + r, fx = tx * BW + col;              // full-image coordinates
+        const int fy = y0 + r, fx = x0 + col;              // full-image coordinates
         if (fy >= H || fx >= W) continue;
         const int py = fy - shave, px = fx - shave;
         const int64_t a = (int64_t)fy * g.sH + (int64_t)fx * g.sW;
@@ -269,7 +228,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float *__restrict__
     }
 }
 
-__global__ void pool_fwd_kernel(const float *__restrict__ X, const float *__restrict__ Y, SsView g, int ho, int wo,
+__global__ void pool_fwd_kernel(const float *__restrict__ X, const float *__restrict__ Y, ImView g, int ho, int wo,
                                 float *__restrict__ Xo, float *__restrict__ Yo) {
     const int64_t total = (int64_t)g.N * g.C * ho * wo;
     const int ph = g.h & 1, pw = g.w & 1;
@@ -295,7 +254,7 @@ __global__ void pool_fwd_kernel(const float *__restrict__ X, const float *__rest
     }
 }
 
-__global__ void pool_bwd_kernel(const float *__restrict__ gc, SsView g, int ho, int wo, float *__restrict__ gf) {
+__global__ void pool_bwd_kernel(const float *__restrict__ gc, ImView g, int ho, int wo, float *__restrict__ gf) {
     const int64_t total = (int64_t)g.N * g.C * g.h * g.w;
     const int ph = g.h & 1, pw = g.w & 1;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -334,14 +293,15 @@ __global__ __launch_bounds__(256) void combine_kernel(const double *__restrict__
             coef[((size_t)l * N + n) * 2 + 1] = l == L - 1 ? 0.f : (float)d;
         }
     }
-    acc = ss_block_sum(acc, sh);
+    acc = tnr_block_sum256(acc, sh);
     if (threadIdx.x == 0) *value = (float)(acc / (double)N);
 }
 
+// SSIM's conditions on top of the dense-batch check: both operands, 1..4 channels, something left after the shave
 int check_image(const char *what, const void *x, const void *y, int N, int C, int H, int W, int layout, int shave) {
     TNR_REQUIRE(x && y, "%s: null pointer", what);
-    TNR_REQUIRE(N > 0 && C >= 1 && C <= 4 && H > 0 && W > 0, "%s: bad shape %d x %d x %d x %d (1..4 channels)", what, N, C, H, W);
-    TNR_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (NCHW) or 1 (channels-last)", what);
+    if (int rc = check_dense(what, N, C, H, W, layout)) return rc;
+    TNR_REQUIRE(C <= 4, "%s: bad shape %d x %d x %d x %d (1..4 channels)", what, N, C, H, W);
     TNR_REQUIRE(shave >= 0 && H - 2 * shave >= 1 && W - 2 * shave >= 1, "%s: nothing left of %d x %d after shave %d", what, H, W, shave);
     return TNR_OK;
 }
@@ -370,13 +330,13 @@ extern "C" int64_t tnr_ssim_workspace_bytes(int32_t N, int32_t C, int32_t H, int
 extern "C" int tnr_ssim_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t shave,
                             const float *taps, int32_t K, float C1, float C2, double *sums, void *ws, int64_t ws_bytes, void *stream) {
     if (int rc = check_image("ssim_fwd", x, y, N, C, H, W, layout, shave)) return rc;
-    const SsView g = make_view(N, C, H, W, layout, shave);
+    const ImView g = make_view(N, C, H, W, layout, shave);
     SsWin win;
     if (int rc = make_window("ssim_fwd", taps, K, g.h, g.w, &win)) return rc;
     TNR_REQUIRE(sums && ws && ws_bytes >= tnr_ssim_workspace_bytes(N, C, H, W, shave, K), "ssim_fwd: workspace missing or too small");
-    const int tilesY = tnr_cdiv(g.h - K + 1, FT), tilesX = tnr_cdiv(g.w - K + 1, FT);
-    const int64_t blocks = (int64_t)N * C * tilesY * tilesX;
-    TNR_REQUIRE(blocks < (1ll << 31), "ssim_fwd: batch too large");
+    int64_t blocks;
+    int tilesX, tilesY;
+    if (int rc = check_batch("ssim_fwd", N, C, g.h - K + 1, g.w - K + 1, layout, FT, FT, &blocks, &tilesX, &tilesY)) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ssim_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, y, g, win, C1, C2, tilesX, tilesY, (double *)ws);
     hipLaunchKernelGGL(ssim_sum_kernel, dim3(N), dim3(256), 0, s, (const double *)ws, C * tilesY * tilesX, sums);
@@ -387,13 +347,13 @@ extern "C" int tnr_ssim_bwd(const float *x, const float *y, int32_t N, int32_t C
                             const float *taps, int32_t K, float C1, float C2, const float *coef, const float *gscale, float *gx,
                             int32_t accumulate, void *stream) {
     if (int rc = check_image("ssim_bwd", x, y, N, C, H, W, layout, shave)) return rc;
-    const SsView g = make_view(N, C, H, W, layout, shave);
+    const ImView g = make_view(N, C, H, W, layout, shave);
     SsWin win;
     if (int rc = make_window("ssim_bwd", taps, K, g.h, g.w, &win)) return rc;
     TNR_REQUIRE(coef && gx, "ssim_bwd: null pointer");
-    const int tilesY = tnr_cdiv(H, BH), tilesX = tnr_cdiv(W, BW);
-    const int64_t blocks = (int64_t)N * C * tilesY * tilesX;
-    TNR_REQUIRE(blocks < (1ll << 31), "ssim_bwd: batch too large");
+    int64_t blocks;
+    int tilesX, tilesY;
+    if (int rc = check_batch("ssim_bwd", N, C, H, W, layout, BW, BH, &blocks, &tilesX, &tilesY)) return rc;
     hipLaunchKernelGGL(ssim_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, y, g, win, C1, C2, coef, gscale, gx,
                        (int)accumulate, (int)shave, tilesX, tilesY);
     return tnr_check_launch("ssim_bwd");
@@ -411,7 +371,7 @@ extern "C" int tnr_avgpool2_pad_fwd(const float *x, const float *y, int32_t N, i
                                     int32_t shave, float *xo, float *yo, void *stream) {
     if (int rc = check_image("avgpool2_pad_fwd", x, y, N, C, H, W, layout, shave)) return rc;
     TNR_REQUIRE(xo && yo, "avgpool2_pad_fwd: null pointer");
-    const SsView g = make_view(N, C, H, W, layout, shave);
+    const ImView g = make_view(N, C, H, W, layout, shave);
     TNR_REQUIRE(g.h >= 2 && g.w >= 2, "avgpool2_pad_fwd: a %d x %d image cannot be pooled", g.h, g.w);
     int ho, wo;
     tnr_avgpool2_pad_dims(H, W, shave, &ho, &wo);
@@ -422,7 +382,7 @@ extern "C" int tnr_avgpool2_pad_fwd(const float *x, const float *y, int32_t N, i
 extern "C" int tnr_avgpool2_pad_bwd(const float *gcoarse, float *gfine, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout,
                                     int32_t shave, void *stream) {
     if (int rc = check_image("avgpool2_pad_bwd", gcoarse, gfine, N, C, H, W, layout, shave)) return rc;
-    const SsView g = make_view(N, C, H, W, layout, shave);
+    const ImView g = make_view(N, C, H, W, layout, shave);
     TNR_REQUIRE(g.h >= 2 && g.w >= 2, "avgpool2_pad_bwd: a %d x %d image cannot be pooled", g.h, g.w);
     int ho, wo;
     tnr_avgpool2_pad_dims(H, W, shave, &ho, &wo);

@@ -9,21 +9,18 @@ eager-PyTorch fallback.
 Both modules memoize within one training step (see `_StepMemo`): the models clear the memo where they clear the networks' forward
 memos (base_model.training_step).
 """
-import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import hip, ops
+from .. import ops
+from ..models.modules._dense import as_layout, dense_layout, gaussian_taps
 
 KERNEL_SIZE = 9
 
 
 def gaussian_taps1d(kernel_size=KERNEL_SIZE, sigma=KERNEL_SIZE / 6.0):
-    """The reference's `get_gaussian_kernel1d` for an odd size (filters.py:85-87), operation for operation: fp64 exponentials rounded
-    to a fp32 tensor, then divided by their fp32 sum."""
-    gauss = torch.Tensor([np.exp(-(x - kernel_size // 2) ** 2 / float(2 * sigma ** 2)) for x in range(kernel_size)])
-    gauss /= gauss.sum()
-    return gauss
+    """The reference's `get_gaussian_kernel1d` for an odd size (filters.py:85-87), operation for operation."""
+    return gaussian_taps(kernel_size, sigma)
 
 
 def gaussian_taps2d(kernel_size=KERNEL_SIZE, sigma=KERNEL_SIZE / 6.0):
@@ -32,29 +29,12 @@ def gaussian_taps2d(kernel_size=KERNEL_SIZE, sigma=KERNEL_SIZE / 6.0):
     return torch.matmul(k.unsqueeze(-1), k.unsqueeze(-1).t())
 
 
-def _layout_of(x, what):
-    hip.require_device(x)
-    if x.dtype != torch.float32 or x.dim() != 4:
-        raise hip.HipEngineError("{}: fp32 N x C x H x W images only (got {} with {} dimensions)".format(what, x.dtype, x.dim()))
-    if x.is_contiguous():
-        return 0
-    if x.permute(0, 2, 3, 1).is_contiguous():
-        return 1
-    raise hip.HipEngineError("{}: the image batch must be NCHW-contiguous or channels-last".format(what))
-
-
-def _as_layout(g, layout):
-    """The incoming gradient in the forward's dense layout (autograd may hand over other strides)."""
-    fmt = torch.channels_last if layout else torch.contiguous_format
-    return g if g.is_contiguous(memory_format=fmt) else g.contiguous(memory_format=fmt)
-
-
 class _LowFn(torch.autograd.Function):
     """L x; backward: L g, the same launch (symmetric taps, zero padding: L is its own adjoint)."""
 
     @staticmethod
     def forward(ctx, x, taps, reuse):
-        layout = _layout_of(x, "FilterLow")
+        layout = dense_layout("FilterLow", x)
         if reuse is not None:
             out = reuse.detach()              # this step's earlier result for the same input values: no launch
         else:
@@ -66,7 +46,7 @@ class _LowFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         layout, taps = ctx.cfg
-        g = _as_layout(g, layout)
+        g = as_layout(g, layout)
         gx = torch.empty_like(g)
         ops.freqsep_low(g, layout, taps, gx)
         return gx, None, None
@@ -77,7 +57,7 @@ class _HighFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, taps, reuse):
-        layout = _layout_of(x, "FilterHigh")
+        layout = dense_layout("FilterHigh", x)
         if reuse is not None:
             out = reuse.detach()
         else:
@@ -91,7 +71,7 @@ class _HighFn(torch.autograd.Function):
     def backward(ctx, g):
         (out,) = ctx.saved_tensors
         layout, taps = ctx.cfg
-        g = _as_layout(g, layout)
+        g = as_layout(g, layout)
         gx = torch.empty_like(out)
         ops.freqsep_high_bwd(g, out, layout, taps, gx)
         return gx, None, None

@@ -19,25 +19,19 @@ from .. import hip, ops
 from ..dataops import filters
 from . import networks
 from .modules import image_losses as IL
+from .modules._dense import dense_layout, gscale
 from .modules.ssim import MS_SSIM, SSIM
 
 
 # ----------------------------------------------------------------------------------------------
 # HIP-backed criteria
 # ----------------------------------------------------------------------------------------------
-def _same_dense_layout(a, b):
-    return a.shape == b.shape and a.stride() == b.stride() and (
-        a.is_contiguous() or (a.dim() == 4 and a.permute(0, 2, 3, 1).is_contiguous()))
-
-
 class _L1MeanFn(torch.autograd.Function):
     """mean(|a - b|): nn.L1Loss(reduction='mean') (losses.py:37-39).  b carries no gradient."""
 
     @staticmethod
     def forward(ctx, a, b):
-        hip.require_device(a)
-        if not _same_dense_layout(a, b):
-            raise hip.HipEngineError("L1: operands must share one dense layout")
+        dense_layout("L1", a, b, any_rank=True)
         out = torch.empty((), dtype=torch.float32, device=a.device)
         ops.l1_mean_fwd(a, b, 1.0, out)
         ctx.save_for_backward(a, b)
@@ -47,7 +41,7 @@ class _L1MeanFn(torch.autograd.Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         ga = torch.empty_like(a)          # preserves a's (possibly channels-last) strides
-        ops.l1_mean_bwd(a, b, 1.0, g.contiguous(), ga)
+        ops.l1_mean_bwd(a, b, 1.0, gscale(g), ga)
         return ga, None
 
 

@@ -13,8 +13,8 @@ import math
 import torch
 import torch.nn as nn
 
-from ... import hip, ops
-from .ssim import _layout_of
+from ... import ops
+from ._dense import dense_layout, gscale
 
 
 def log_kernel_taps(kernel_size=15, sigma=2.5):
@@ -36,21 +36,12 @@ def log_kernel_taps(kernel_size=15, sigma=2.5):
 # ----------------------------------------------------------------------------------------------
 # autograd functions
 # ----------------------------------------------------------------------------------------------
-def _gscale(g):
-    return g.float().reshape(1).contiguous()
-
-
 class _PointFn(torch.autograd.Function):
     """scale * sum rho(a - b) over two tensors of one dense layout.  b carries no gradient."""
 
     @staticmethod
     def forward(ctx, a, b, crit, scale):
-        hip.require_device(a)
-        if a.dtype != torch.float32 or b.dtype != torch.float32:
-            raise hip.HipEngineError("pixel criterion: fp32 operands only (got {} / {})".format(a.dtype, b.dtype))
-        if a.shape != b.shape or a.stride() != b.stride() or not (
-                a.is_contiguous() or (a.dim() == 4 and a.permute(0, 2, 3, 1).is_contiguous())):
-            raise hip.HipEngineError("pixel criterion: operands must share one dense layout")
+        dense_layout("pixel criterion", a, b, any_rank=True)
         out = torch.empty((), dtype=torch.float32, device=a.device)
         ops.pointwise_loss_fwd(a, b, crit, scale, out)
         ctx.save_for_backward(a, b)
@@ -61,7 +52,7 @@ class _PointFn(torch.autograd.Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         ga = torch.empty_like(a)          # preserves a's (possibly channels-last) strides
-        ops.pointwise_loss_bwd(a, b, ctx.cfg[0], ctx.cfg[1], _gscale(g), ga)
+        ops.pointwise_loss_bwd(a, b, ctx.cfg[0], ctx.cfg[1], gscale(g), ga)
         return ga, None, None, None
 
 
@@ -70,7 +61,7 @@ class _FilterFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, taps, K, crit, scale):
-        layout = _layout_of(x, y, "HFEN")
+        layout = dense_layout("HFEN", x, y)
         out = torch.empty((), dtype=torch.float32, device=x.device)
         dmap = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         ops.filter_loss_fwd(x, y, layout, taps, K, crit, scale, out, dmap)
@@ -83,7 +74,7 @@ class _FilterFn(torch.autograd.Function):
         (dmap,) = ctx.saved_tensors
         layout, taps, K, scale = ctx.cfg
         gx = torch.empty_like(dmap)
-        ops.filter_loss_bwd(dmap, layout, taps, K, scale, _gscale(g), gx)
+        ops.filter_loss_bwd(dmap, layout, taps, K, scale, gscale(g), gx)
         return gx, None, None, None, None, None
 
 
@@ -92,7 +83,7 @@ class _FdFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, dirs, crit, scale):
-        layout = _layout_of(x, x if y is None else y, "image gradients")
+        layout = dense_layout("image gradients", x, *(() if y is None else (y,)))
         out = torch.empty((), dtype=torch.float32, device=x.device)
         ops.fd_loss_fwd(x, y, layout, dirs, crit, scale, out)
         ctx.save_for_backward(x, y)
@@ -104,7 +95,7 @@ class _FdFn(torch.autograd.Function):
         x, y = ctx.saved_tensors
         layout, dirs, crit, scale = ctx.cfg
         gx = torch.empty_like(x)
-        ops.fd_loss_bwd(x, y, layout, dirs, crit, scale, _gscale(g), gx)
+        ops.fd_loss_bwd(x, y, layout, dirs, crit, scale, gscale(g), gx)
         return gx, None, None, None, None
 
 

@@ -10,24 +10,14 @@ X carries the gradient, Y (the HR batch) is data.  Both are fp32 N x C x H x W i
 worked out on the host from the shape, once per shape.
 """
 import functools
-import math
 
 import torch
 import torch.nn as nn
 
 from ... import hip, ops
+from ._dense import dense_layout, gaussian_taps, gscale
 
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
-
-
-def gaussian_taps(size, sigma):
-    """The reference's 1-D window (dataops/filters.py:84-87): exp(-(x - size // 2)^2 / (2 sigma^2)) rounded to fp32, then
-    normalised in fp32.  Returns a fp32 tensor of `size` taps."""
-    if not isinstance(size, int) or size <= 0 or size % 2 == 0:
-        raise TypeError("kernel_size must be an odd positive integer. Got {}".format(size))
-    g = torch.tensor([math.exp(-(x - size // 2) ** 2 / float(2 * sigma ** 2)) for x in range(size)], dtype=torch.float32)
-    g /= g.sum()
-    return g
 
 
 def pooled_size(h, w):
@@ -66,19 +56,6 @@ def _taps_list(size, sigma):
     return tuple(float(v) for v in gaussian_taps(size, sigma))
 
 
-def _layout_of(x, y, what):
-    hip.require_device(x)
-    if x.dtype != torch.float32 or y.dtype != torch.float32:
-        raise hip.HipEngineError("{}: fp32 images only (got {} / {})".format(what, x.dtype, y.dtype))
-    if x.shape != y.shape or x.stride() != y.stride():
-        raise hip.HipEngineError("{}: operands must share one dense layout".format(what))
-    if x.is_contiguous():
-        return 0
-    if x.permute(0, 2, 3, 1).is_contiguous():
-        return 1
-    raise hip.HipEngineError("{}: operands must be NCHW-contiguous or channels-last".format(what))
-
-
 def _constants(data_range, K):
     return float((K[0] * data_range) ** 2), float((K[1] * data_range) ** 2)
 
@@ -88,7 +65,7 @@ class _SSIMFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, shave, taps, C1, C2):
-        layout = _layout_of(x, y, "SSIM")
+        layout = dense_layout("SSIM", x, y)
         N, C, H, W = x.shape
         k = len(taps)
         dev = x.device
@@ -108,7 +85,7 @@ class _SSIMFn(torch.autograd.Function):
         x, y, coef = ctx.saved_tensors
         layout, shave, taps, C1, C2 = ctx.cfg
         gx = torch.empty_like(x)          # preserves x's (possibly channels-last) strides
-        ops.ssim_bwd(x, y, layout, shave, taps, C1, C2, coef, g.float().contiguous(), gx)
+        ops.ssim_bwd(x, y, layout, shave, taps, C1, C2, coef, gscale(g), gx)
         return gx, None, None, None, None, None
 
 
@@ -120,7 +97,7 @@ class _MSSSIMFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, shave, geom, weights, C1, C2):
-        layout = _layout_of(x, y, "MS-SSIM")
+        layout = dense_layout("MS-SSIM", x, y)
         N, C = x.shape[:2]
         dev = x.device
         L = len(geom)
@@ -150,7 +127,7 @@ class _MSSSIMFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             raise hip.HipEngineError("MS-SSIM: no gradient is implemented for the second operand (the HR batch is data)")
         C1, C2 = ctx.consts
-        g = g.float().contiguous()
+        g = gscale(g)
         coarse = None
         coef, images = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         for i in range(len(ctx.meta) - 1, -1, -1):

@@ -1093,14 +1093,19 @@ def linear_bwd(x, w, gy, yact=None, gx=None, dw=None, db=None, acc_beta=1.0, msl
 # ----------------------------------------------------------------------------------------------
 # losses / optimiser
 # ----------------------------------------------------------------------------------------------
-def _red_ws(device):
-    lib = hip.load()
-    return WS.get("red", lib.tnr_reduce_workspace_bytes(), device)
+def _reduce_ws(dev):
+    """The fp64 partials of the two-stage reductions, one buffer per stream: two streams may reduce at the same time."""
+    return WS.get("reduce@%x" % hip.stream(), hip.load().tnr_reduce_workspace_bytes(), dev)
+
+
+def _floats(seq, n=None):
+    """Python floats (filter taps, level weights) as the ctypes array of n (default: all of them) fp32 values the library reads."""
+    return (C.c_float * (len(seq) if n is None else n))(*seq)
 
 
 def l1_mean_fwd(a, b, scale, out):
     hip.check(hip.load().tnr_l1_mean_fwd(a.data_ptr(), b.data_ptr(), a.numel(), scale, out.data_ptr(),
-                                         _red_ws(a.device).data_ptr(), hip.stream()), "l1_mean_fwd")
+                                         _reduce_ws(a.device).data_ptr(), hip.stream()), "l1_mean_fwd")
 
 
 def l1_mean_bwd(a, b, scale, gscale, ga, accumulate=False):
@@ -1108,17 +1113,14 @@ def l1_mean_bwd(a, b, scale, gscale, ga, accumulate=False):
                                          int(accumulate), hip.stream()), "l1_mean_bwd")
 
 
-# SSIM / MS-SSIM training losses (csrc/ssim_loss.hip).  x, y: fp32 N x C x H x W in one dense layout (`layout` 0 NCHW-contiguous,
-# 1 channels-last); taps: the window as a sequence of K Python floats (already rounded to fp32).
-def _ssim_taps(taps):
-    return (C.c_float * len(taps))(*taps), len(taps)
-
-
+# Image-space losses and filters (csrc/ssim_loss.hip, image_losses.hip, freqsep.hip).  x, y and every other image operand: fp32
+# N x C x H x W in one dense layout (`layout` 0 NCHW-contiguous, 1 channels-last); taps: Python floats already rounded to fp32.
+# A backward writes gx in x's layout, times gscale[0] (None = 1).
 def ssim_fwd(x, y, layout, shave, taps, C1, C2, sums):
     """sums[n] (fp64 [N, 2]) = {sum ssim_map, sum cs_map} of image n."""
     lib = hip.load()
     N, Ch, H, W = x.shape
-    arr, K = _ssim_taps(taps)
+    arr, K = _floats(taps), len(taps)
     nbytes = lib.tnr_ssim_workspace_bytes(N, Ch, H, W, shave, K)
     ws = WS.get("ssim@%x" % hip.stream(), nbytes, x.device)
     hip.check(lib.tnr_ssim_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, shave, arr, K, C1, C2, sums.data_ptr(), ws.data_ptr(),
@@ -1127,7 +1129,7 @@ def ssim_fwd(x, y, layout, shave, taps, C1, C2, sums):
 
 def ssim_bwd(x, y, layout, shave, taps, C1, C2, coef, gscale, gx, accumulate=False):
     N, Ch, H, W = x.shape
-    arr, K = _ssim_taps(taps)
+    arr, K = _floats(taps), len(taps)
     hip.check(hip.load().tnr_ssim_bwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, shave, arr, K, C1, C2, coef.data_ptr(),
                                       hip.ptr(gscale), gx.data_ptr(), int(accumulate), hip.stream()), "ssim_bwd")
 
@@ -1152,14 +1154,13 @@ def avgpool2_pad_bwd(gcoarse, gfine, layout, shave):
 
 def msssim_combine(sums, levels, N, counts, weights, mode, value, coef):
     cnt = (C.c_int64 * levels)(*counts)
-    wts = (C.c_float * levels)(*weights) if weights is not None else None
+    wts = _floats(weights, levels) if weights is not None else None
     hip.check(hip.load().tnr_msssim_combine(sums.data_ptr(), levels, N, cnt, wts, mode, value.data_ptr(), coef.data_ptr(),
                                             hip.stream()), "msssim_combine")
 
 
-# HFEN / image-gradient / total-variation / difference-only pixel losses (csrc/image_losses.hip).  x, y as for the ssim wrappers;
-# crit: one of the CRIT_* numbers; every forward writes loss (1 float) = scale * sum rho(e), every backward gx (x's layout) =
-# scale * gscale[0] * d sum rho / dx (gscale None = 1).
+# HFEN / image-gradient / total-variation / difference-only pixel losses.  crit: one of the CRIT_* numbers; every forward writes
+# loss (1 float) = scale * sum rho(e), every backward gx = scale * gscale[0] * d sum rho / dx.
 CRIT_L1, CRIT_L2, CRIT_CB, CRIT_ELASTIC, CRIT_CLIPL1 = 0, 1, 2, 3, 4
 
 
@@ -1172,14 +1173,14 @@ def filter_loss_fwd(x, y, layout, taps, K, crit, scale, loss, dmap=None):
     """taps: K * K Python floats, row-major.  dmap (x's shape and layout, or None) receives rho'(L * (x - y))."""
     N, Ch, H, W = x.shape
     ws = _imgloss_ws(x)
-    hip.check(hip.load().tnr_filter_loss_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, (C.c_float * (K * K))(*taps), K, crit,
+    hip.check(hip.load().tnr_filter_loss_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, _floats(taps, K * K), K, crit,
                                              float(scale), loss.data_ptr(), hip.ptr(dmap), ws.data_ptr(), ws.numel() * 8, hip.stream()),
               "filter_loss_fwd")
 
 
 def filter_loss_bwd(dmap, layout, taps, K, scale, gscale, gx, accumulate=False):
     N, Ch, H, W = dmap.shape
-    hip.check(hip.load().tnr_filter_loss_bwd(dmap.data_ptr(), N, Ch, H, W, layout, (C.c_float * (K * K))(*taps), K, float(scale),
+    hip.check(hip.load().tnr_filter_loss_bwd(dmap.data_ptr(), N, Ch, H, W, layout, _floats(taps, K * K), K, float(scale),
                                              hip.ptr(gscale), gx.data_ptr(), int(accumulate), hip.stream()), "filter_loss_bwd")
 
 
@@ -1207,30 +1208,26 @@ def pointwise_loss_bwd(a, b, crit, scale, gscale, ga, accumulate=False):
                                                 int(accumulate), hip.stream()), "pointwise_loss_bwd")
 
 
-# Frequency separation (csrc/freqsep.hip): the zero-padded 9 x 9 low-pass L from its 9 separable taps (Python floats) and the
-# separator high-pass clamp((x - L x + 1) / 2, 0, 1).  x / g / o / out: fp32 N x C x H x W in one dense layout; one launch each.
+# Frequency separation: the zero-padded 9 x 9 low-pass L from its 9 separable taps and the separator high-pass
+# clamp((x - L x + 1) / 2, 0, 1); one launch each.
 def freqsep_low(x, layout, taps9, out, gscale=None, accumulate=False):
     """out (+)= gscale[0] * (L x): FilterLow's forward and, L being its own adjoint, its backward."""
     N, Ch, H, W = x.shape
-    hip.check(hip.load().tnr_freqsep_low(x.data_ptr(), N, Ch, H, W, layout, (C.c_float * 9)(*taps9), hip.ptr(gscale), out.data_ptr(),
+    hip.check(hip.load().tnr_freqsep_low(x.data_ptr(), N, Ch, H, W, layout, _floats(taps9, 9), hip.ptr(gscale), out.data_ptr(),
                                          int(accumulate), hip.stream()), "freqsep_low")
 
 
 def freqsep_high_fwd(x, layout, taps9, out):
     N, Ch, H, W = x.shape
-    hip.check(hip.load().tnr_freqsep_high_fwd(x.data_ptr(), N, Ch, H, W, layout, (C.c_float * 9)(*taps9), out.data_ptr(), hip.stream()),
+    hip.check(hip.load().tnr_freqsep_high_fwd(x.data_ptr(), N, Ch, H, W, layout, _floats(taps9, 9), out.data_ptr(), hip.stream()),
               "freqsep_high_fwd")
 
 
 def freqsep_high_bwd(g, o, layout, taps9, gx, gscale=None, accumulate=False):
     """gx (+)= gscale[0] * (g' - L g'), g' = 0.5 g where the forward's saved output o is strictly inside (0, 1)."""
     N, Ch, H, W = g.shape
-    hip.check(hip.load().tnr_freqsep_high_bwd(g.data_ptr(), o.data_ptr(), N, Ch, H, W, layout, (C.c_float * 9)(*taps9), hip.ptr(gscale),
+    hip.check(hip.load().tnr_freqsep_high_bwd(g.data_ptr(), o.data_ptr(), N, Ch, H, W, layout, _floats(taps9, 9), hip.ptr(gscale),
                                               gx.data_ptr(), int(accumulate), hip.stream()), "freqsep_high_bwd")
-
-
-def _reduce_ws(dev):
-    return WS.get("reduce@%x" % hip.stream(), hip.load().tnr_reduce_workspace_bytes(), dev)
 
 
 def ragan_phase_a(pf, pr, sums):
@@ -1253,7 +1250,7 @@ def scale_by(dst, src, gscale):
 
 
 def sumsq(g, out):
-    hip.check(hip.load().tnr_sumsq(g.data_ptr(), g.numel(), out.data_ptr(), _red_ws(g.device).data_ptr(), hip.stream()),
+    hip.check(hip.load().tnr_sumsq(g.data_ptr(), g.numel(), out.data_ptr(), _reduce_ws(g.device).data_ptr(), hip.stream()),
               "sumsq")
 
 
