@@ -253,7 +253,9 @@ int tnr_conv_chain(const tnr_conv_desc *stages, const int32_t *fresh_from, int32
  * which stays valid until those change.  tnr_conv_sweep_image_bytes returns 0 when the stages are not such a block (or an
  * image's tiles exceed the co-resident workgroups): use tnr_conv_chain then.  ws / epoch as for tnr_conv_chain (same buffer,
  * same counter; the buffer also holds the launch's tile dispenser, which every launch leaves at zero: one launch at a time per ws,
- * i.e. one ws per stream).  Results are bit-identical to tnr_conv_chain / five tnr_conv_forward calls in TNR_MMA_BF16X3.    */
+ * i.e. one ws per stream).  Results are bit-identical to tnr_conv_chain / five tnr_conv_forward calls in TNR_MMA_BF16X3.
+ * n = 4 (TNR_MMA_BF16X3, the default four-wave direct form only): the first four stages of such a block -- 32 output channels each --
+ * with an image of their own; bit-identical to four tnr_conv_forward calls.                                                 */
 int64_t tnr_conv_sweep_image_bytes(const tnr_conv_desc *stages, int32_t n);
 int tnr_conv_sweep_pack(const tnr_conv_desc *stages, int32_t n, void *image, int64_t image_bytes, void *stream);
 /* the images of MANY blocks in one launch: tnr_conv_sweep_pack_item validates a block like tnr_conv_sweep_pack and fills one HOST entry

@@ -34,6 +34,9 @@
 // image; never more than the tiles of one image, which the grid always covers), not the whole grid.  Waits are bounded either way (fault latch, tnr_set_fault_word).
 // Arithmetic (split, kept partial products and their order, channel and tap order, epilogue) is that of conv_tile_body<.., BF = 2>:
 // results are bit-identical to five tnr_conv_forward launches in TNR_MMA_BF16X3.
+// FOUR stages (n = 4, direct four-wave form only; SwPlan4 below): the block's conv1 .. conv4 with the same hand-off, dispenser, waits
+// and arithmetic -- bit-identical to four tnr_conv_forward launches; the caller runs the 64-wide last stage as a launch of its own
+// (ops.dense_block: the Winograd kernel).  Still one workgroup per CU; the progress argument above holds with 3 (tiles_x + 1) + 1.
 #include <stddef.h>
 #include <string.h>
 #include <type_traits>
@@ -88,6 +91,46 @@ constexpr bool sw_plan_ok() {
 }
 
 static_assert(sw_plan_ok(), "sweep plan");
+
+// The FOUR-stage plan (conv_sweep4_kernel<true, false, SwPlan4>): a dense block's conv1 .. conv4 -- or stages 1 .. 4 of its gradient
+// mirror -- with the 64-wide last stage left to a launch of its own (the Winograd kernel, conv_wino.hip).  N-tile j = x_{j+1}; the same
+// a / b pass structure: pass 2 f computes the stage that completes in phase f first (its epilogue is issued right behind it), pass
+// 2 f + 1 the remaining N-tiles of the phase while those stores drain and the neighbours catch up; the last phase has one pass.  A
+// phase WITHOUT a pass b would have to load its successor's first chunk -- this tile's and its neighbours' fresh output -- before
+// the epilogue that produces it has been issued, so phase 2 is two one-tile passes rather than one pass of two.  18 stagings per tile
+// for 252 units (the five-stage plan: 22 for 468), 128 accumulator registers per lane instead of 192.
+//                                       pass:  0  1  2  3  4  5  6
+constexpr int SW4_NPASS = 7, SW4_NSTAGE = 4, SW4_NTILE = 4;
+constexpr int SW4_J0[SW4_NPASS] =             { 0, 2, 1, 3, 2, 3, 3 };
+constexpr int SW4_NJ[SW4_NPASS] =             { 2, 2, 2, 1, 1, 1, 1 };
+__host__ __device__ constexpr int sw4_nj_rt(int p) { return p < 3 ? 2 : 1; }
+__host__ __device__ constexpr int sw4_j0_rt(int p) { return p == 0 ? 0 : (p == 2 ? 1 : ((p == 1 || p == 4) ? 2 : 3)); }
+constexpr bool sw4_plan_ok() {
+    for (int p = 0; p < SW4_NPASS; ++p) {
+        if (sw4_nj_rt(p) != SW4_NJ[p] || sw4_j0_rt(p) != SW4_J0[p]) return false;
+        if (sw_apass(p) && SW4_J0[p] != sw_phase(p)) return false;                                   // pass a starts at the completing stage's N-tile
+        if (!sw_apass(p) && SW4_J0[p] != SW4_J0[p - 1] + SW4_NJ[p - 1]) return false;               // pass b continues where pass a stopped
+        if ((!sw_apass(p) || p == SW4_NPASS - 1) && SW4_J0[p] + SW4_NJ[p] != SW4_NTILE) return false;      // ... up to the last N-tile
+    }
+    return true;
+}
+static_assert(sw4_plan_ok(), "four-stage sweep plan");
+
+// A plan as a compile-time parameter of conv_sweep4_kernel (phase = pass / 2 and pass a = even pass in both).
+struct SwPlan5 {
+    static constexpr int NPASS = SW_NPASS, NSTAGE = SW_NSTAGE, NTILE = SW_NTILE;
+    static constexpr int j0(int p) { return SW_J0[p]; }
+    static constexpr int nj(int p) { return SW_NJ[p]; }
+};
+struct SwPlan4 {
+    static constexpr int NPASS = SW4_NPASS, NSTAGE = SW4_NSTAGE, NTILE = SW4_NTILE;
+    static constexpr int j0(int p) { return SW4_J0[p]; }
+    static constexpr int nj(int p) { return SW4_NJ[p]; }
+};
+// (run-time stage count ns = 5 / 4: the pack kernels and the host)
+__host__ __device__ constexpr int sw_npass_rt(int ns) { return ns == 4 ? SW4_NPASS : SW_NPASS; }
+__host__ __device__ constexpr int sw_nj_rt(int p, int ns) { return ns == 4 ? sw4_nj_rt(p) : sw_nj_rt(p); }
+__host__ __device__ constexpr int sw_j0_rt(int p, int ns) { return ns == 4 ? sw4_j0_rt(p) : sw_j0_rt(p); }
 static_assert(SW_J0[1] == SW_J0[3] && SW_NJ[1] == SW_NJ[3] && SW_TT[1] == SW_TT[3] && SW_J0[5] == SW_J0[8] && SW_NJ[5] == SW_NJ[8] && SW_TT[5] == SW_TT[8], "passes 1 / 3 and 5 / 8 share a body");
 
 struct SweepK {
@@ -105,9 +148,9 @@ struct SweepK {
 
 __host__ __device__ inline int sw_nchunks(int p, int nck0) { return sw_phase(p) == 0 ? nck0 : 2; }
 __host__ __device__ inline int sw_ch_lo(int p, int nck0) { return sw_phase(p) == 0 ? 0 : 16 * nck0 + 32 * (sw_phase(p) - 1); }
-__host__ __device__ inline int sw_total_units(int nck0) {
+__host__ __device__ inline int sw_total_units(int nck0, int ns = SW_NSTAGE) {
     int u = 0;
-    for (int p = 0; p < SW_NPASS; ++p) u += sw_nchunks(p, nck0) * 9 * sw_nj_rt(p);
+    for (int p = 0; p < sw_npass_rt(ns); ++p) u += sw_nchunks(p, nck0) * 9 * sw_nj_rt(p, ns);
     return u;
 }
 
@@ -117,6 +160,7 @@ __host__ __device__ inline int sw_total_units(int nck0) {
 struct SweepPackK {
     int nck0, units;
     int direct;                        // 1: the register image of the direct form (conv_sweep4_kernel<true>), 0: the LDS image
+    int ns;                            // stages: 5, or 4 (the four-stage plan)
     const float *wp[SW_NSTAGE];
     int KinP[SW_NSTAGE], KoutP[SW_NSTAGE];
     float *out;
@@ -126,14 +170,14 @@ __device__ __forceinline__ void sweep_pack_one(const SweepPackK &a, const int g)
     const int unit = g >> 6, r = (g >> 1) & 31, sp = g & 1;
     if (unit >= a.units) return;
     int p = 0, u0 = 0;
-    for (; p < SW_NPASS; ++p) {
-        const int n = sw_nchunks(p, a.nck0) * 9 * sw_nj_rt(p);
+    for (; p < sw_npass_rt(a.ns); ++p) {
+        const int n = sw_nchunks(p, a.nck0) * 9 * sw_nj_rt(p, a.ns);
         if (unit < u0 + n) break;
         u0 += n;
     }
-    const int lu = unit - u0, nj = sw_nj_rt(p);
+    const int lu = unit - u0, nj = sw_nj_rt(p, a.ns);
     const int jj = lu % nj, ct = lu / nj, tap = ct % 9, ck = ct / 9;
-    const int j = sw_j0_rt(p) + jj;
+    const int j = sw_j0_rt(p, a.ns) + jj;
     const int s = j < 4 ? j : 4, cb = j == 5 ? 1 : 0;
     const int h = sp ^ ((r >> TNR_X3_SWZ) & 1);
     const int ch = sw_ch_lo(p, a.nck0) + 16 * ck + 8 * h;
@@ -523,11 +567,12 @@ __device__ __forceinline__ void sw_static_for(F &&f) {
 // three MFMAs of unit g (`b_fetch`; the four waves of a CU ask for the same lines within a few hundred cycles: one L2 read, three L1
 // hits).  No weight ring in LDS, no LDS-DMA pieces (60 cycles of issue each: +230 cycles on 2 units of every slot), no slot
 // synchronisations (two per chunk at ~550 cycles) -- profiles/r03ap_sweep4_units.txt priced those at 14 % of the kernel.
-template <int J0, int NJ, bool DIRECT, class Sync, class Item, class Dma, class Tick, class BFetch>
-__device__ __forceinline__ void sweep4_chunk(f32x16 (&acc)[2][SW_NTILE], const float *sa, const float *s_b_lane, const int (&apix0)[2],
+template <int J0, int NJ, bool DIRECT, int NT, class Sync, class Item, class Dma, class Tick, class BFetch>
+__device__ __forceinline__ void sweep4_chunk(f32x16 (&acc)[2][NT], const float *sa, const float *s_b_lane, const int (&apix0)[2],
                                              const int half, Sync &&sync, Item &&item_step, Dma &&dma_step, Tick &&tick,
                                              tnr_bf16x8 (&fbr)[3][3], BFetch &&b_fetch) {
     static_assert((9 * NJ) % 3 == 0, "a chunk starts at ring position 0");
+    static_assert(J0 >= 0 && J0 + NJ <= NT, "the chunk's N-tiles are accumulators of the kernel");
     constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};      // the six kept partial products, smallest first
     constexpr int NU = 9 * NJ, SU = 3 * NJ;
     tnr_bf16x8 fa[2][2][3], fb[2][3];
@@ -603,8 +648,8 @@ __device__ __forceinline__ void sweep4_chunk(f32x16 (&acc)[2][SW_NTILE], const f
 // round-to-nearest bf16 weight, the input tile's hi plane the rounded activation (the stager skips the other two).  With units this
 // short the fragment ring is nine deep (unit g + 8 is fetched behind the first MFMA of unit g: ~500 cycles of look-ahead, an L2 hit),
 // one whole input-chunk item (convert + one 8-byte LDS store) rides behind the second MFMA of the chunk's last units.
-template <int J0, int NJ, class Item, class BFetch>
-__device__ __forceinline__ void amp4_chunk(f32x16 (&acc)[2][SW_NTILE], const float *sa, const int (&apix0)[2], const int half,
+template <int J0, int NJ, int NT, class Item, class BFetch>
+__device__ __forceinline__ void amp4_chunk(f32x16 (&acc)[2][NT], const float *sa, const int (&apix0)[2], const int half,
                                            Item &&item, tnr_bf16x8 (&fbq)[9], BFetch &&b_fetch) {
     constexpr int NU = 9 * NJ;
     static_assert(NU % 9 == 0, "a chunk starts at ring position 0");
@@ -644,9 +689,10 @@ __device__ __forceinline__ void amp4_chunk(f32x16 (&acc)[2][SW_NTILE], const flo
 #ifndef S4D_ALOAD_ALWAYS
 #define S4D_ALOAD_ALWAYS 1    /* direct form: the next chunk's input loads on every path (0: only when there is a next chunk) */
 #endif
-template <bool DIRECT, bool AMP = false>
+template <bool DIRECT, bool AMP = false, class P = SwPlan5>
 __global__ void __launch_bounds__(256, 1) conv_sweep4_kernel(const SweepK c) {
     static_assert(DIRECT || !AMP, "the bf16-operand form exists as a direct form only");
+    static_assert(std::is_same<P, SwPlan5>::value || (DIRECT && !AMP), "the four-stage plan exists in the direct bf16x3 form only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *s_a = smem, *s_b = smem + 2 * SW_A_FLOATS;
     const int tid = threadIdx.x;
@@ -781,11 +827,11 @@ __global__ void __launch_bounds__(256, 1) conv_sweep4_kernel(const SweepK c) {
             }
         };
 
-        f32x16 acc[2][SW_NTILE];
+        f32x16 acc[2][P::NTILE];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int j = 0; j < SW_NTILE; ++j)
+            for (int j = 0; j < P::NTILE; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
 
@@ -928,7 +974,7 @@ __global__ void __launch_bounds__(256, 1) conv_sweep4_kernel(const SweepK c) {
 
         // The nine passes are unrolled in the source: every accumulator access and every stage index is a compile-time constant, and
         // the control flow the register allocator sees is a plain sequence of chunk loops.
-        sw_static_for<0, SW_NPASS>([&](auto pc) __attribute__((always_inline)) {
+        sw_static_for<0, P::NPASS>([&](auto pc) __attribute__((always_inline)) {
             constexpr int p = decltype(pc)::value;
             const int nchunks = sw_nchunks(p, c.nck0), ch_lo = sw_ch_lo(p, c.nck0);
 #pragma unroll 1
@@ -939,13 +985,13 @@ __global__ void __launch_bounds__(256, 1) conv_sweep4_kernel(const SweepK c) {
                     if (ck == 0) epilogue_of(std::integral_constant<int, sw_phase(p)>{});
                 }
                 const bool last_ck = ck + 1 == nchunks;
-                has_next = !(last_ck && p == SW_NPASS - 1);
+                has_next = !(last_ck && p == P::NPASS - 1);
                 int ch_keep = 0;
                 if (has_next) {
                     int ch_next = ch_lo + 16 * (ck + 1);
                     if (last_ck) {
-                        ch_next = sw_ch_lo(p + 1 < SW_NPASS ? p + 1 : p, c.nck0);
-                        if constexpr (p + 1 < SW_NPASS && sw_apass(p + 1)) {
+                        ch_next = sw_ch_lo(p + 1 < P::NPASS ? p + 1 : p, c.nck0);
+                        if constexpr (p + 1 < P::NPASS && sw_apass(p + 1)) {
                             // the first chunk of the next phase is the output of the stage this tile and its 8 neighbours finished
                             // in pass a of the current phase
                             const ChainWait w{c.progress, c.base + (unsigned)sw_phase(p + 1), n, ty, tx, c.tiles_x, c.tiles_y, c.err,
@@ -976,14 +1022,14 @@ __global__ void __launch_bounds__(256, 1) conv_sweep4_kernel(const SweepK c) {
                     auto item1 = [&](auto ic) __attribute__((always_inline)) {
                         if (has_next) a_item1(ic, (e + 1) & 1);
                     };
-                    amp4_chunk<sw_j0(p), sw_nj(p)>(acc, sa, apix0, half, item1, fbq, b_fetch1);
+                    amp4_chunk<P::j0(p), P::nj(p)>(acc, sa, apix0, half, item1, fbq, b_fetch1);
                 } else {
-                    sweep4_chunk<sw_j0(p), sw_nj(p), DIRECT>(acc, sa, s_b_lane, apix0, half, sync, item_step, dma_step, tick, fbr, b_fetch);
+                    sweep4_chunk<P::j0(p), P::nj(p), DIRECT>(acc, sa, s_b_lane, apix0, half, sync, item_step, dma_step, tick, fbr, b_fetch);
                 }
-                { SW_T(t_c1); SW_ADD(6, t_c1 - t_c0); SW_ADD(15, 1ull); SW_ADD(9 + (sw_nj(p) == 3 ? 0 : (sw_nj(p) == 2 ? 1 : 2)), t_c1 - t_c0); }
+                { SW_T(t_c1); SW_ADD(6, t_c1 - t_c0); SW_ADD(15, 1ull); SW_ADD(9 + (P::nj(p) == 3 ? 0 : (P::nj(p) == 2 ? 1 : 2)), t_c1 - t_c0); }
                 ++e;
             }
-            if constexpr (DIRECT && S4D_EPI_AFTER && sw_apass(p) && p + 1 < SW_NPASS) {
+            if constexpr (DIRECT && S4D_EPI_AFTER && sw_apass(p) && p + 1 < P::NPASS) {
                 // direct form: the epilogue of the stage this pass completed stands BEHIND the pass's chunk loop, on every path -- under
                 // `if (ck == 0)` at the top of the next pass the compiler must assume, at the join, that the fragment ring is the
                 // youngest thing in the memory queue and makes the first unit wait for the epilogue's stores.  Published two chunk tops
@@ -991,7 +1037,7 @@ __global__ void __launch_bounds__(256, 1) conv_sweep4_kernel(const SweepK c) {
                 epilogue_of(std::integral_constant<int, sw_phase(p)>{});
             }
         });
-        epilogue_of(std::integral_constant<int, 4>{});      // the last stage (pass 8 is a pass a)
+        epilogue_of(std::integral_constant<int, P::NSTAGE - 1>{});      // the last stage (the last pass is a pass a)
     }
     // nothing in this launch waits for the last stage; publish it anyway so the counters stay consistent
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1468,10 +1514,12 @@ bool d4_ok(const tnr_conv_desc *d) {
 }
 
 // Do the stages form a dense block the sweep kernel covers?  (5 stages over ONE input buffer, stage k reading channels [0, nf + 32 k)
-// and -- except the last -- writing the next 32 channels of that buffer; 32, 32, 32, 32, 64 output channels)
+// and -- except the last -- writing the next 32 channels of that buffer; 32, 32, 32, 32, 64 output channels.  n = 4: the first four of
+// them -- the four-stage plan, bf16x3 only.)
 bool sweep_pattern(const tnr_conv_desc *st, int n, const char **why) {
     auto no = [&](const char *w) { if (why) *why = w; return false; };
-    if (n != SW_NSTAGE) return no("not 5 stages");
+    if (st == nullptr || (n != SW_NSTAGE && n != SW4_NSTAGE)) return no("not 5 (or 4) stages");
+    if (n == SW4_NSTAGE && st[0].mma != TNR_MMA_BF16X3) return no("the four-stage form exists in bf16x3 only");
     const tnr_conv_desc &d0 = st[0];
     if (d0.Cin < 32 || (d0.Cin % 16) != 0) return no("block input channels must be a multiple of 16, >= 32");
     for (int i = 0; i < n; ++i) {
@@ -1492,7 +1540,7 @@ bool sweep_pattern(const tnr_conv_desc *st, int n, const char **why) {
         if (!d.x.ptr || !d.y.ptr || !d.wp) return no("null pointer");
     }
     const tnr_conv_desc &dl = st[n - 1];
-    if (dl.y.ptr == d0.x.ptr && dl.y.coff < d0.x.coff + dl.Cin && dl.y.coff + dl.Cout > d0.x.coff) return no("last stage overwrites its own input");
+    if (n == SW_NSTAGE && dl.y.ptr == d0.x.ptr && dl.y.coff < d0.x.coff + dl.Cin && dl.y.coff + dl.Cout > d0.x.coff) return no("last stage overwrites its own input");
     return true;
 }
 
@@ -1520,6 +1568,8 @@ int sweep_cus() {
             hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)S4D_LDS_BYTES) != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep4_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)S4D_LDS_BYTES) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep4_kernel<true, false, SwPlan4>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)S4D_LDS_BYTES) != hipSuccess || cus < 1)
             cus = -1;
     }
@@ -1549,11 +1599,11 @@ extern "C" int tnr_debug_sweep_timeline(unsigned long long *out16, int reset) {
 
 extern "C" int64_t tnr_conv_sweep_image_bytes(const tnr_conv_desc *stages, int32_t n) {
     if (stages == nullptr || !sweep_pattern(stages, n, nullptr)) return 0;
-    if (stages[0].mma == TNR_MMA_BF16 && sweep_form() != 5) return 0;      // bf16 operands: the direct four-wave form only
+    if ((stages[0].mma == TNR_MMA_BF16 || n == SW4_NSTAGE) && sweep_form() != 5) return 0;      // bf16 operands, four stages: the direct four-wave form only
     const int cus = sweep_cus();
     const int tpi = tnr_cdiv(stages[0].W, SW_TW) * tnr_cdiv(stages[0].H, SW_TH);
     if (cus < 1 || tpi > cus) return 0;          // an image's tiles must be co-resident (one workgroup per CU)
-    return (int64_t)sw_total_units(stages[0].Cin / 16) * SW_UNIT_FLOATS * (int64_t)sizeof(float);
+    return (int64_t)sw_total_units(stages[0].Cin / 16, n) * SW_UNIT_FLOATS * (int64_t)sizeof(float);
 }
 
 extern "C" int tnr_conv_sweep_pack(const tnr_conv_desc *stages, int32_t n, void *image, int64_t image_bytes, void *stream) {
@@ -1561,13 +1611,16 @@ extern "C" int tnr_conv_sweep_pack(const tnr_conv_desc *stages, int32_t n, void 
     TNR_REQUIRE(stages != nullptr && image != nullptr && sweep_pattern(stages, n, &why), "conv_sweep_pack: not a sweepable dense block (%s)", why);
     SweepPackK a;
     a.nck0 = stages[0].Cin / 16;
-    a.units = sw_total_units(a.nck0);
+    a.ns = n;
+    a.units = sw_total_units(a.nck0, n);
     a.direct = sweep_form() == 5;
     TNR_REQUIRE((int64_t)a.units * SW_UNIT_FLOATS * (int64_t)sizeof(float) <= image_bytes, "conv_sweep_pack: image buffer too small");
+    TNR_REQUIRE(n == SW_NSTAGE || a.direct, "conv_sweep_pack: four stages run in the direct four-wave form only");
     for (int i = 0; i < SW_NSTAGE; ++i) {
-        a.wp[i] = stages[i].wp;
-        a.KinP[i] = stages[i].KinP;
-        a.KoutP[i] = stages[i].KoutP;
+        const tnr_conv_desc &d = stages[i < n ? i : n - 1];          // (four stages: the fifth entry is never read)
+        a.wp[i] = d.wp;
+        a.KinP[i] = d.KinP;
+        a.KoutP[i] = d.KoutP;
     }
     a.out = static_cast<float *>(image);
     hipLaunchKernelGGL(sweep_pack_kernel, dim3((unsigned)tnr_cdiv(a.units * 64, 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -1582,13 +1635,16 @@ extern "C" int tnr_conv_sweep_pack_item(const tnr_conv_desc *stages, int32_t n, 
                 "conv_sweep_pack_item: not a sweepable dense block (%s)", why);
     SweepPackK a;
     a.nck0 = stages[0].Cin / 16;
-    a.units = sw_total_units(a.nck0);
+    a.ns = n;
+    a.units = sw_total_units(a.nck0, n);
     a.direct = sweep_form() == 5;
     TNR_REQUIRE((int64_t)a.units * SW_UNIT_FLOATS * (int64_t)sizeof(float) <= image_bytes, "conv_sweep_pack_item: image buffer too small");
+    TNR_REQUIRE(n == SW_NSTAGE || a.direct, "conv_sweep_pack_item: four stages run in the direct four-wave form only");
     for (int i = 0; i < SW_NSTAGE; ++i) {
-        a.wp[i] = stages[i].wp;
-        a.KinP[i] = stages[i].KinP;
-        a.KoutP[i] = stages[i].KoutP;
+        const tnr_conv_desc &d = stages[i < n ? i : n - 1];
+        a.wp[i] = d.wp;
+        a.KinP[i] = d.KinP;
+        a.KoutP[i] = d.KoutP;
     }
     a.out = static_cast<float *>(image);
     memset(item, 0, sizeof(*item));
@@ -1627,9 +1683,9 @@ extern "C" int tnr_conv_sweep(const tnr_conv_desc *stages, int32_t n, const void
     c.disp = ws + (ws_bytes / 4 - 1 - 4 - CH_CU_KEYS - CH_SWEEP_WORDS);      // (words of their own, zero-initialised; every launch leaves them at zero)
     c.base = epoch * (uint32_t)(TNR_CHAIN_MAX + 2);
     c.wq = static_cast<const float *>(image);
-    c.wq_bytes = sw_total_units(c.nck0) * SW_UNIT_FLOATS * (int)sizeof(float);
+    c.wq_bytes = sw_total_units(c.nck0, n) * SW_UNIT_FLOATS * (int)sizeof(float);
     for (int i = 0; i < SW_NSTAGE; ++i) {
-        const tnr_conv_desc *d = &stages[i];
+        const tnr_conv_desc *d = &stages[i < n ? i : n - 1];         // (four stages: the fifth entry is never read)
         ConvK &k = c.st[i];
         k.x = d->x.ptr; k.x_ct = d->x.ctot; k.x_co = d->x.coff;
         k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin;
@@ -1648,6 +1704,11 @@ extern "C" int tnr_conv_sweep(const tnr_conv_desc *stages, int32_t n, const void
     const int per_round = (cus / c.tpi) * c.tpi;
     const int grid = c.tiles < per_round ? c.tiles : per_round;
     const int form = sweep_form();
+    if (n == SW4_NSTAGE) {
+        TNR_REQUIRE(form == 5, "conv_sweep: four stages run in the direct four-wave form only");
+        hipLaunchKernelGGL((conv_sweep4_kernel<true, false, SwPlan4>), dim3((unsigned)grid), dim3(256), S4D_LDS_BYTES, (hipStream_t)stream, c);
+        return tnr_check_launch("conv_sweep");
+    }
     if (stages[0].mma == TNR_MMA_BF16) {
         TNR_REQUIRE(form == 5, "conv_sweep: bf16 operands (use_amp) run in the direct four-wave form only");
         hipLaunchKernelGGL((conv_sweep4_kernel<true, true>), dim3((unsigned)grid), dim3(256), S4D_LDS_BYTES, (hipStream_t)stream, c);

@@ -145,7 +145,7 @@ class RRDBNet(HipNet):
                                              r2=View(bufs[(i - 2) % nbuf], 0, nf), alpha2=0.2, **nk))
             else:
                 st.append(convs[4].fwd_stage(View(buf), dst, fresh_from=nf + 3 * gc, alpha=0.2, r1=View(buf, 0, nf), **nk))
-            ops.conv_chain(st)
+            ops.dense_block(st)
         y0 = new_act(N, h, w, nf, dev)
         o["lr"].fwd(View(trunk), View(y0), r1=fea_keep)          # ShortcutBlock: fea + trunk(fea)
         cur, stages = View(y0), []
@@ -223,7 +223,7 @@ class RRDBNet(HipNet):
         if nz_out is not None:
             kw["noise"] = nz_out.at(2)
         st.append(dict(x=View(GP), wp=dp.get(dense[4]), y=gnext, fresh_from=nf + 3 * gc, r1=g, beta1=s, **kw))
-        ops.conv_chain(st)                       # one launch for the block's data-gradient (conv_chain.hip)
+        ops.dense_block(st)                      # the block's data-gradient: one launch (conv_chain.hip), or four stages + a Winograd launch
         if want_w:
             # Weight gradients are only COLLECTED here and launched per RRDB (_flush_wgrads): conv5 as 64 x 64 channel
             # workgroup tiles; conv1..conv4 (32 couts; g_k lives at GP[nf + (3-k)*gc : +gc)) as 32 x 128 / 32 x 64 /

@@ -177,6 +177,7 @@ class DensePacker:
     def _finalize(self):
         self.__dict__.pop("_sweep_images", None)
         self.__dict__.pop("_sweep_batch", None)
+        self.__dict__.pop("_wq_images", None)          # (dense_block: the transform-domain stream of the mirror's last stage)
         total = sum(round_up(j[7], 64) for j in self.jobs)
         self.flat = torch.empty(total, dtype=torch.float32, device=self.device)
         items = (DensePackItem * len(self.jobs))()
@@ -354,8 +355,8 @@ def _wq_image(lib, d, wp, dev, tag=None):
 # to the direct kernels).  The transform + operand split of an input chunk is vector-ALU work per PIXEL that only 64 output channels per
 # workgroup amortise (registers: 16 transform positions x 2 x 2 accumulator tiles), so the kernel is bound by it, not by the matrix
 # core: x 1.19 (128 ch) / 1.26 (256) / 1.23-1.31 (512) over the direct weight-stream kernel, x 1.04-1.11 on the 64-channel layers
-# (profiles/r09o_wino_blate_ab.txt; analysis DESIGN.md 3.9).  Dense blocks never use it (their per-layer fallback must stay
-# bit-identical to the one-launch forms).  TNR_WINO=0: off.
+# (profiles/r09o_wino_blate_ab.txt; analysis DESIGN.md 3.9).  conv_chain never uses it (its per-layer fallback must stay
+# bit-identical to the one-launch forms); dense_block may run a block's 64-wide last stage in it (TNR_DENSE_SPLIT).  TNR_WINO=0: off.
 WINO = os.environ.get("TNR_WINO", "1") != "0"
 WINO_MIN_CIN = int(os.environ.get("TNR_WINO_MIN_CIN", "64"))
 WINO_MIN_PIXELS = int(os.environ.get("TNR_WINO_MIN_PIXELS", "4096"))
@@ -651,7 +652,8 @@ def conv_chain(stages):
     # workgroups guarantee progress (21 on the 128-wide trunk, never more than the tiles of one image): it may
     # stay one launch -- opt-in (TNR_DP_OVERLAP_G=1, models/sr_model.py) until a multi-GPU run has exercised it.
     crowded = COLLECTIVES_IN_FLIGHT and not CHAIN_WITH_COLLECTIVES
-    sweep_ok = CONV_SWEEP and n == 5 and ((MMA == hip.MMA_BF16X3 and CHAIN_X3) or (MMA == hip.MMA_BF16 and AMP_SWEEP))
+    # (n == 4: a block's first four stages -- the four-stage plan of the sweep, bf16x3 only; dense_block runs the fifth on its own)
+    sweep_ok = CONV_SWEEP and ((n in (4, 5) and MMA == hip.MMA_BF16X3 and CHAIN_X3) or (n == 5 and MMA == hip.MMA_BF16 and AMP_SWEEP))
     auto = SWEEP_AUTO and CONV_CHAIN and eligible and sweep_ok and MMA == hip.MMA_BF16X3 and stages[0]["x"].buf.is_cuda
     if auto and SWEEP_AUTO_STATE["choice"] == "layers":      # (calibrate_dense_block_form chose it at model set-up: never timed here)
         for st in stages:
@@ -689,9 +691,9 @@ def conv_chain(stages):
         fill(ws[:-1].view(torch.float32), 0.0)         # (stream-ordered after every earlier launch on this stream)
         _chain_epoch[key] = 1
     image = None
-    if CONV_SWEEP and n == 5 and (descs[0].mma == hip.MMA_BF16X3 or (descs[0].mma == hip.MMA_BF16 and AMP_SWEEP)):
+    if CONV_SWEEP and ((n in (4, 5) and descs[0].mma == hip.MMA_BF16X3) or (n == 5 and descs[0].mma == hip.MMA_BF16 and AMP_SWEEP)):
         image = _sweep_image(lib, descs, n, stages, dev)
-    if crowded and image is None:                      # (a 5-stage block the sweep does not cover: shapes, tiles per image)
+    if crowded and image is None:                      # (a block the sweep does not cover: shapes, tiles per image)
         COUNTERS["per_layer_next_to_collectives"] += 1
         for st in stages:
             conv(wino=False, **{k: v for k, v in st.items() if k != "fresh_from"})      # (the direct kernels: bit-identical to the one-launch forms)
@@ -706,6 +708,59 @@ def conv_chain(stages):
     if PROFILE is not None:
         x0, yl = stages[0]["x"], stages[-1]["y"]
         PROFILE.end("conv_chain", flops, t0, (x0.C, yl.C, yl.H, stages[0]["wp"].kind))
+
+
+# TNR_MMA=bf16x3: a dense block as a FOUR-stage sweep (conv1 .. conv4, or stages 1 .. 4 of the gradient mirror: conv_chain(stages[:4]))
+# plus its 64-wide last stage -- 46 % of the block's multiply-adds -- as a Winograd F(2x2, 3x3) launch (2.25 x fewer matrix
+# instructions; conv_wino.hip).  x1 .. x4 stay bit-identical to conv_chain's; the block output carries the Winograd form's error (<= 3 x
+# the fp32 matrix core's against fp64, as everywhere that form runs) and is deterministic.  The five-stage sweep's time is set by the
+# matrix core's dynamic energy, so the instructions removed are what pays.  Measured: DESIGN.md 3.2.  0: conv_chain(stages).
+DENSE_SPLIT = os.environ.get("TNR_DENSE_SPLIT", "1") != "0"
+_SWEEP_FORM_DMA = os.environ.get("TNR_SWEEP_FORM", "")[:2] == "dm"
+_cu_counts = {}
+
+
+def _cus(dev):
+    n = _cu_counts.get(dev)
+    if n is None:
+        n = _cu_counts[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return n
+
+
+def dense_split_applies(stages):
+    """Does dense_block run `stages` in the split form?  A function of the arithmetic, the process switches, the agreed dense-block
+    form and the block's PER-IMAGE grid and channel counts -- never of the batch size (data-parallel shards of one global batch pick
+    the same form as one process would)."""
+    if not (DENSE_SPLIT and CONV_CHAIN and CONV_SWEEP and SWEEP_DISPENSED and CHAIN_X3 and MMA == hip.MMA_BF16X3 and len(stages) == 5):
+        return False
+    x0, yl = stages[0]["x"], stages[4]["y"]
+    if not x0.buf.is_cuda or _SWEEP_FORM_DMA:          # (the four-stage plan exists in the direct four-wave form only)
+        return False
+    if SWEEP_AUTO and SWEEP_AUTO_STATE["choice"] == "layers":
+        return False
+    if COLLECTIVES_IN_FLIGHT and not CHAIN_WITH_COLLECTIVES:
+        return False
+    if not all(st.get("mode", CONV_3x3) == CONV_3x3 and not st.get("reflect") and st["wp"].KoutP == st["y"].C and st["wp"].KinP == st["x"].C
+               for st in stages):
+        return False
+    if yl.C != 64 or any(st["y"].C != 32 for st in stages[:4]) or x0.C % 16 or x0.C < 32 or stages[4]["x"].C != x0.C + 128:
+        return False
+    # the sweep keeps an image's 8 x 32 tiles co-resident (one workgroup per CU); the Winograd kernel wants an 8 x 8 grid at least
+    return x0.H >= 8 and x0.W >= 8 and -(-x0.W // 32) * -(-x0.H // 8) <= _cus(x0.buf.device)
+
+
+def dense_block(stages):
+    """A residual dense block's five convolutions (or the five of its gradient mirror): conv_chain(stages), or -- where
+    dense_split_applies -- the four-stage sweep followed by the last stage in the Winograd form."""
+    if not dense_split_applies(stages):
+        return conv_chain(stages)
+    last = {k: v for k, v in stages[4].items() if k != "fresh_from"}
+    out = last["y"]
+    for v in _stage_views(last):       # a Winograd tile reads a halo of its input (and residuals other workgroups' pixels never touch --
+        if v is not out and v.buf.data_ptr() == out.buf.data_ptr():          # kept to the same rule): the output shares no channel with anything read
+            assert min(v.coff + v.C, out.coff + out.C) <= max(v.coff, out.coff), "dense_block: the output view overlaps a view the last stage reads"
+    conv_chain(stages[:4])
+    conv(wino=True, **last)
 
 
 _FAULT = None
