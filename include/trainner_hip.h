@@ -586,6 +586,21 @@ int tnr_freqsep_high_fwd(const float *x, int32_t N, int32_t C, int32_t H, int32_
 int tnr_freqsep_high_bwd(const float *g, const float *o, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const float *taps9,
                          const float *gscale, float *gx, int32_t accumulate, void *stream);
 
+/* --- Gram matrix of an activation (GramMatrix(out_norm='ci'), modules/loss.py:479-506: the style term of PerceptualLoss,
+ * losses.py:311-326; csrc/gram.hip) -----------------------------------------------------------------------------------------------
+ * x: an NHWC view [N, H, W, C], C a multiple of 64 up to 512.  mma: TNR_MMA_F32 or TNR_MMA_BF16X3 (operands split once, in the stager).
+ * tnr_gram_fwd: G[n][i][j] = scale * sum over the H W pixels p of x[n][p][i] x[n][p][j], G dense fp32 [N, C, C] (the caller passes
+ *   scale = 1 / (C H W)).  The pixels are split over workgroups into partial 64 x 64 tiles of the block upper triangle in ws
+ *   (tnr_gram_workspace_bytes), which a second launch adds in a fixed order and mirrors: G is bit-exactly symmetric and two runs are
+ *   bit-identical (no floating-point atomics).
+ * tnr_gram_bwd: dx[n][p][c] = scale * sum_j x[n][p][j] (S[n][j][c] + S[n][c][j]) for S = d loss / d G ([N, C, C], need not be
+ *   symmetric: the stager forms S + S^T); written into the view dx, or added to what is there when `accumulate`. */
+int64_t tnr_gram_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C);
+int tnr_gram_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, int32_t C, float scale, int32_t mma, float *G, float *ws, int64_t ws_bytes,
+                 void *stream);
+int tnr_gram_bwd(tnr_view x, const float *S, int32_t N, int32_t H, int32_t W, int32_t C, float scale, int32_t mma, tnr_view dx,
+                 int32_t accumulate, void *stream);
+
 /* --- optimiser (torch.optim.Adam optimizers.py:130-132; clip_grad_norm_ base_model.py:911-922) -- */
 int tnr_sumsq(const float *g, int64_t n, double *out, void *ws, void *stream);
 int tnr_clip_by_norm(float *g, int64_t n, const double *sumsq, float max_norm, void *stream);

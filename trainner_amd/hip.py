@@ -187,6 +187,9 @@ _SIGS = {
     "tnr_freqsep_low": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),
     "tnr_freqsep_high_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p]),
     "tnr_freqsep_high_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),
+    "tnr_gram_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i]),
+    "tnr_gram_fwd": (c_i, [CView, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p]),
+    "tnr_gram_bwd": (c_i, [CView, c_p, c_i, c_i, c_i, c_i, c_f, c_i, CView, c_i, c_p]),
     "tnr_sumsq": (c_i, [c_p, c_l, c_p, c_p, c_p]),
     "tnr_clip_by_norm": (c_i, [c_p, c_l, c_p, c_f, c_p]),
     "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),

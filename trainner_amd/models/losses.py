@@ -3,8 +3,9 @@
 Keeps the reference's surface (codes/models/losses.py): `get_loss_fn` -> {'name','weight','function'},
 `PerceptualLoss` (:220-340), `Adversarial` (:343-604) and `GeneratorLoss` (:607-962) with the same
 option keys, loss names (`pix-l1`, `fea-vgg19-l1`) and weighting order, restricted to the branches the
-ESRGAN recipe uses (options/sr/train_sr.yml:107-110,145-146): L1 pixel loss, VGG19 conv5_4 L1
-perceptual loss, vanilla relativistic GAN, plus the SSIM / MS-SSIM term of the "precise" list
+ESRGAN recipe uses (options/sr/train_sr.yml:107-110,145-146): L1 pixel loss, the VGG L1 perceptual
+loss over any dictionary of layers (`perceptual_opt.perceptual_layers`) and the Gram-matrix style loss
+(`style_weight`, `perceptual_opt.style_layers`; csrc/gram.hip), vanilla relativistic GAN, plus the SSIM / MS-SSIM term of the "precise" list
 (`ssim_type` / `ssim_weight`, losses.py:798-802) and the recipe's edge / smoothness terms
 (train_sr.yml:114-120): the difference-only pixel criteria l2, cb, elastic and clipl1, HFEN (`hfen_criterion` /
 `hfen_weight`), total variation (`tv_type` / `tv_norm` / `tv_weight`) and the image-gradient loss of the precise list
@@ -43,6 +44,32 @@ class _L1MeanFn(torch.autograd.Function):
         ga = torch.empty_like(a)          # preserves a's (possibly channels-last) strides
         ops.l1_mean_bwd(a, b, 1.0, gscale(g), ga)
         return ga, None
+
+
+class _GramFn(torch.autograd.Function):
+    """GramMatrix(out_norm='ci') (modules/loss.py:479-506): gram[n] = F F^T / (C H W) for F = the feature map as a C x HW matrix.
+    `fea` is a logical NCHW tensor over NHWC storage, as the FeatureExtractor hands it out.  The kernels read the fp32 activations and
+    run in the TNR_MMA arithmetic with or without `use_amp`: stricter than the reference, whose autocast runs this product in half
+    precision."""
+
+    @staticmethod
+    def forward(ctx, fea):
+        hip.require_device(fea)
+        N, C, H, W = fea.shape
+        x = fea.detach().permute(0, 2, 3, 1)
+        x = ops.View(x if x.is_contiguous() else x.contiguous())
+        G = torch.empty((N, C, C), dtype=torch.float32, device=fea.device)
+        ctx.scale = 1.0 / (C * H * W)
+        ops.gram_fwd(x, ctx.scale, G)
+        ctx.save_for_backward(x.buf)
+        return G
+
+    @staticmethod
+    def backward(ctx, S):
+        (xb,) = ctx.saved_tensors
+        dx = torch.empty_like(xb)
+        ops.gram_bwd(ops.View(xb), S.contiguous(), ctx.scale, ops.View(dx))
+        return dx.permute(0, 3, 1, 2)
 
 
 class L1Loss(nn.Module):
@@ -213,12 +240,13 @@ def check_loss_names(feature_criterion=None, feature_network=None, hfen_criterio
 
 
 class PerceptualLoss(nn.Module):
-    """VGG feature (perceptual) loss; style loss / random flips are not on the path (losses.py:220-340)."""
+    """VGG feature (perceptual) loss and Gram-matrix style loss over dictionaries of layers (losses.py:220-340).  The random
+    rotations / flips of `perceptual_opt` are refused."""
 
     def __init__(self, criterion=None, network=None, opt=None):
         super().__init__()
         self.criterion, self.network = criterion, network
-        w_l_p = {"conv5_4": 1}
+        w_l_p, w_l_s = {"conv5_4": 1}, {}
         self.perceptual_weight, self.style_weight = 1.0, 0.0
         if opt:
             train_opt = opt["train"]
@@ -227,11 +255,15 @@ class PerceptualLoss(nn.Module):
             perc_opts = train_opt.get("perceptual_opt")
             if perc_opts:
                 w_l_p = perc_opts.get("perceptual_layers", {"conv5_4": 1})
-                if perc_opts.get("rotations") or perc_opts.get("flips") or perc_opts.get("style_layers"):
-                    raise NotImplementedError("perceptual_opt rotations/flips/style are not implemented by the HIP engine")
+                w_l_s = perc_opts.get("style_layers", {})
+                for k in ("rotations", "flips"):
+                    if perc_opts.get(k):
+                        raise NotImplementedError("perceptual_opt '{}' is not implemented by the HIP engine".format(k))
+        # losses.py:281-293: an empty dictionary falls back on the other term's
         if self.style_weight > 0:
-            raise NotImplementedError("style loss is not implemented by the HIP engine")
-        self.w_l_p = w_l_p
+            self.w_l_s = w_l_p if (not w_l_s and w_l_p) else w_l_s
+        if self.perceptual_weight > 0:
+            self.w_l_p = w_l_s if (not w_l_p and w_l_s) else w_l_p
 
     def forward(self, x, y):
         fea_x = self.network(x)
@@ -243,7 +275,17 @@ class PerceptualLoss(nn.Module):
             for k in self.w_l_p.keys():
                 percep_loss = percep_loss + self.criterion(fea_x[k], fea_y[k]) * self.w_l_p[k]
             percep_loss = percep_loss * self.perceptual_weight
-        return percep_loss, None
+        style_loss = None
+        if self.style_weight > 0:
+            # Data parallelism needs no collective here: a Gram matrix belongs to ONE image and the L1 over [N, C, C] is a batch mean
+            # over equal shards, so the ranks' averaged gradient is the global-batch gradient (see GeneratorLoss._log)
+            style_loss = 0
+            for k in self.w_l_s.keys():
+                with torch.no_grad():
+                    gram_y = _GramFn.apply(fea_y[k])
+                style_loss = style_loss + self.criterion(_GramFn.apply(fea_x[k]), gram_y) * self.w_l_s[k]
+            style_loss = style_loss * self.style_weight
+        return percep_loss, style_loss
 
 
 class Adversarial(nn.Module):
@@ -345,7 +387,7 @@ class GeneratorLoss(nn.Module):
     order and names."""
 
     _UNSUPPORTED = ("color_weight", "avg_weight", "ms_weight", "spl_weight", "of_weight",
-                    "style_weight", "lpips_weight", "cx_weight", "fft_weight",
+                    "lpips_weight", "cx_weight", "fft_weight",
                     "fdpl_weight", "range_weight")
 
     def __init__(self, opt=None, device="cpu", allow_featnets=True):
@@ -368,11 +410,12 @@ class GeneratorLoss(nn.Module):
         if tv_weight > 0 and tv_type:
             self.loss_list.append(get_loss_fn(tv_type, tv_weight, device=device))
         feature_weight = (train_opt.get("feature_weight", 0) or 0) if allow_featnets else 0
+        style_weight = (train_opt.get("style_weight", 0) or 0) if allow_featnets else 0
         feat_opts = train_opt.get("perceptual_opt")
         feature_network = (feat_opts or {}).get("feature_network", None) or train_opt.get("feature_network", "vgg19") or "vgg19"
         feature_criterion = check_loss_names(feature_criterion=train_opt.get("feature_criterion"),
                                              feature_network=feature_network)
-        if feature_weight > 0 and feature_criterion:
+        if (feature_weight > 0 or style_weight > 0) and feature_criterion:          # losses.py:735
             self.loss_list.append(get_loss_fn(feature_criterion, 1, opt=opt, device=device))
             self.cri_fea = True
         else:
@@ -402,6 +445,15 @@ class GeneratorLoss(nn.Module):
         effective = l["weight"] * value
         if self.dp_group is not None and getattr(l["function"], "sum_reduced", False):
             effective = effective * float(self.dp_group.world_size)
+        return effective
+
+    @staticmethod
+    def _fea_effective(l, percep_loss, style_loss):
+        """losses.py:849-856: weight * percep + weight * style under the one log name; a None term (its weight is 0) is skipped."""
+        effective = None
+        for term in (percep_loss, style_loss):
+            if term is not None:
+                effective = l["weight"] * term if effective is None else effective + l["weight"] * term
         return effective
 
     def _log(self, log_dict, name, effective):
@@ -436,8 +488,7 @@ class GeneratorLoss(nn.Module):
             elif "ssim" in name:
                 effective = l["weight"] * (1 - f(lp("sr", sr), lp("hr", hr)))
             elif "fea-vgg" in name:
-                percep_loss, _ = f(sr, hr)                                          # unfiltered
-                effective = l["weight"] * percep_loss
+                effective = self._fea_effective(l, *f(sr, hr))                      # unfiltered
             else:
                 # everything else sees the unfiltered pair.  That includes grad-2d-* / grad-4d-*: the reference's low-pass branch asks
                 # for 'gradient' in the name (losses.py:879), which these names do not contain -- its quirk, kept
@@ -480,8 +531,7 @@ class GeneratorLoss(nn.Module):
         results = []
         for l in self.loss_list:
             if "fea-vgg" in l["name"]:
-                percep_loss, _ = l["function"](sr, hr)
-                effective = l["weight"] * percep_loss
+                effective = self._fea_effective(l, *l["function"](sr, hr))
             elif "tv" in l["name"]:
                 effective = self._effective(l, l["function"](self._fp32(sr)))              # fake_H alone
             elif isinstance(l["function"], (IL.HFENLoss, IL._Criterion)):

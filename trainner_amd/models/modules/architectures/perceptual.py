@@ -1,10 +1,21 @@
-"""VGG feature extractor for the perceptual loss, on the MI355X engine.
+"""VGG feature extractor for the perceptual and style losses, on the MI355X engine.
 
 Follows codes/models/modules/architectures/perceptual.py FeatureExtractor (:73-214): ImageNet
 (x-mean)/std, torchvision cfg-E/D `features` truncated after the last listened layer, listened
 features taken BEFORE the ReLU when a 'convX_Y' name is listened (the `x.clone()` at :211-212
 happens before the in-place ReLU that follows).  Parameters are frozen (requires_grad False,
 :185-188): only the data-gradient schedule exists.
+
+`listen_list` is any non-empty set of convX_Y / reluX_Y / poolX names.  One forward taps the network at
+every listened layer and returns {name: feature} in network order; it is ONE autograd node with one
+output per tap, and its backward is one reverse sweep that takes one gradient per tap (absent ones are
+skipped) and injects it where the tap was taken: a relu or pool tap's gradient joins the running
+gradient before that layer's derivative, a conv tap's after the ReLU mask of the layer above.  No
+convolution runs twice.  A conv tap below the last layer costs one elementwise pass (its pre-ReLU map is
+the tap, relu(map) feeds the next layer); an injected gradient costs one (conv, pool) or two (relu: mask,
+then add) elementwise passes.  The configuration with one conv tap that is also the last layer (the
+ESRGAN recipe's conv5_4) runs the launches it always ran.  Still refused, by name: remove_pooling,
+change_padding, requires_grad, z_norm (and rotations / flips in PerceptualLoss, which draw random numbers).
 
 torchvision is not a dependency of the kernels: the layer table is the public VGG configuration.
 Weights: `load_path` (a torchvision `vggNN` state_dict, keys `features.N.*`) when given, else
@@ -52,17 +63,25 @@ class FeatureExtractor(HipNet):
     def __init__(self, listen_list=None, net="vgg19", use_input_norm=True, z_norm=False, requires_grad=False,
                  remove_pooling=False, pooling_stride=2, change_padding=False, load_path=None, allow_random_init=False):
         super().__init__()
-        if net not in VGG_CFG or remove_pooling or pooling_stride != 2 or change_padding or requires_grad or z_norm:
-            raise NotImplementedError("FeatureExtractor option outside the ESRGAN recipe is not implemented by the HIP engine")
+        for opt_name, on in (("remove_pooling", remove_pooling), ("change_padding", change_padding), ("requires_grad", requires_grad),
+                             ("z_norm", z_norm)):
+            if on:
+                raise NotImplementedError("FeatureExtractor option '%s' is not implemented by the HIP engine" % opt_name)
+        if net not in VGG_CFG or pooling_stride != 2:
+            raise NotImplementedError("FeatureExtractor net=%r / pooling_stride=%r is not implemented by the HIP engine" % (net, pooling_stride))
         listen_list = list(listen_list or ["conv5_4"])
-        if len(listen_list) != 1 or not listen_list[0].startswith("conv"):
-            raise NotImplementedError("the HIP FeatureExtractor listens to exactly one pre-ReLU conv layer")
-        self.listen = listen_list[0]
+        names = vgg_layer_names(net)
+        unknown = [v for v in listen_list if v not in names]
+        if unknown:
+            raise ValueError("FeatureExtractor(%s): unknown layer name(s) %s" % (net, ", ".join(map(str, unknown))))
         self.listen_list = set(listen_list)
         self.use_input_norm = use_input_norm
-        names = vgg_layer_names(net)
-        last = names.index(self.listen)
+        last = max(names.index(v) for v in listen_list)       # truncated after the last listened layer (perceptual.py:129-144)
         self.names = names[:last + 1]
+        self.taps = [n for n in self.names if n in self.listen_list]      # network order
+        # one conv tap that is also the last layer: the single-output node and launch sequence this class always had
+        self._single = len(self.taps) == 1 and self.taps[0].startswith("conv")
+        self.listen = self.taps[0] if self._single else None
         layers, c, chans = nn.ModuleDict(), 3, iter([v for v in VGG_CFG[net] if v != "M"])
         for n in self.names:
             if n.startswith("conv"):
@@ -192,6 +211,129 @@ class FeatureExtractor(HipNet):
         ops.nhwc_to_nchw(View(g.buf, 0, 3), out, scale=scale)
         return out
 
+    # ---- any number of taps -------------------------------------------------------------------------------------------
+    def engine_forward_taps(self, x, save):
+        """The sweep of engine_forward with a tap at every listened layer.  tape: (name, input view, output view the next layer reads)
+        per conv / pool; feats: name -> view."""
+        N, Cc, H, W = x.shape
+        if Cc != 3:
+            raise ValueError("FeatureExtractor expects RGB input")
+        dev = x.device
+        scale, shift = self._norm_consts(dev)
+        x4 = View(new_act(N, H, W, 4, dev))
+        ops.nchw_to_nhwc(x, x4, Cpad=4, scale=scale, shift=shift)
+        cur, tape, feats = x4, [], {}
+        for i, n in enumerate(self.names):
+            if n.startswith("conv"):
+                y = View(new_act(N, cur.H, cur.W, self.feature_net[n].out_channels, dev))
+                if n not in self.listen_list:
+                    self._ops[n].fwd(cur, y, act=ops.ACT_RELU)
+                else:
+                    self._ops[n].fwd(cur, y)                              # listened pre-ReLU
+                    feats[n] = y
+                    if i + 1 < len(self.names):                           # the network goes on: relu(map) in one elementwise pass
+                        post = View(new_act(N, y.H, y.W, y.C, dev))
+                        ops.mask_copy(post, y, y, mslope=0.0)             # y * (y > 0)
+                        y = post
+                tape.append((n, cur, y))
+                cur = y
+            elif n.startswith("pool"):
+                y = View(new_act(N, cur.H // 2, cur.W // 2, cur.C, dev))
+                ops.maxpool2_fwd(cur, y)
+                tape.append((n, cur, y))
+                cur = y
+                if n in self.listen_list:
+                    feats[n] = y
+            elif n in self.listen_list:                                   # reluX_Y: the post-ReLU map the next layer reads
+                feats[n] = cur
+        outs = tuple(feats[n].buf.permute(0, 3, 1, 2) for n in self.taps)
+        return outs, (dict(tape=tape, in_shape=(N, H, W)) if save else None)
+
+    @staticmethod
+    def _grad_view(g):
+        g_nhwc = g.permute(0, 2, 3, 1)
+        return View(g_nhwc if g_nhwc.is_contiguous() else g_nhwc.contiguous())
+
+    def _inject(self, entry, tg, g):
+        """Add the tap gradients of `entry`'s output maps to the running gradient g (None: nothing arrived from above yet), in the
+        running form: with respect to the PRE-activation map for a conv (the ReLU mask of the layer above already applied to what
+        came through it), to the pooled map for a pool.  Tap gradients are never written to."""
+        n, _, y = entry
+        dev = y.buf.device
+
+        def add(g, t):
+            if g is None:
+                return t
+            if any(g is v for v in tg.values()):                          # still a caller's tensor: sum into a fresh buffer
+                s = View(new_act(y.N, y.H, y.W, y.C, dev))
+                ops.add2(s, g, t)
+                return s
+            ops.axpby(g, t, 1.0, 1.0)
+            return g
+
+        if n.startswith("pool"):
+            return add(g, tg[n]) if tg.get(n) is not None else g
+        tr = tg.get("relu" + n[4:])
+        if tr is not None:                                                # before the ReLU's derivative: mask it, then add
+            m = View(new_act(y.N, y.H, y.W, y.C, dev))
+            ops.mask_copy(m, tr, y, mslope=0.0)                           # y is the post-ReLU map here: same sign pattern as the pre-ReLU one
+            g = m if g is None else add(g, m)
+        if tg.get(n) is not None:                                         # conv tap: after the mask
+            g = add(g, tg[n])
+        return g
+
+    def engine_backward_taps(self, sv, gouts):
+        tape = sv["tape"]
+        N, H, W = sv["in_shape"]
+        tg = {n: self._grad_view(g) for n, g in zip(self.taps, gouts) if g is not None}
+        dev = tape[0][1].buf.device
+        g = self._inject(tape[-1], tg, None)
+        for i in range(len(tape) - 1, -1, -1):
+            n, xin, y = tape[i]
+            if g is not None:
+                gx = View(new_act(N, xin.H, xin.W, xin.C, dev))
+                if n.startswith("pool"):
+                    ops.maxpool2_bwd(g, xin, gx)                          # routes + ReLU' of the pooled activation
+                else:
+                    prev = tape[i - 1][0] if i > 0 else None
+                    if prev is not None and prev.startswith("conv"):
+                        self._ops[n].dgrad(g, gx, mask=xin, m_slope=0.0)  # ReLU' of the producing conv
+                    else:
+                        self._ops[n].dgrad(g, gx)                         # input image / pooled map: no activation
+                g = gx
+            if i > 0:
+                g = self._inject(tape[i - 1], tg, g)
+        out = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
+        if g is None:
+            return out.zero_()
+        scale, _ = self._norm_consts(dev)
+        ops.nhwc_to_nchw(View(g.buf, 0, 3), out, scale=scale)
+        return out
+
     def forward(self, x):
-        feat = super().forward(x)
-        return {self.listen: feat}
+        if self._single:
+            return {self.listen: super().forward(x)}
+        x = x.contiguous()
+        self._prepare(x)
+        feats = _TapsFn.apply(self, x, *self.parameters())
+        return dict(zip(self.taps, feats))
+
+
+class _TapsFn(torch.autograd.Function):
+    """The multi-tap extractor as ONE autograd node with one output per listened layer (the frozen parameters are listed as inputs
+    like in engine._NetFn; they get no gradient)."""
+
+    @staticmethod
+    def forward(ctx, net, x, *params):
+        ctx.set_materialize_grads(False)                  # a tap no loss term reads arrives as None and is skipped
+        outs, saved = net.engine_forward_taps(x, save=ctx.needs_input_grad[1])
+        ctx.net, ctx.saved = net, saved
+        return outs
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        saved, ctx.saved = ctx.saved, None
+        if saved is None:
+            raise RuntimeError("HIP engine: backward through a forward that saved no activations")
+        gx = ctx.net.engine_backward_taps(saved, gouts) if ctx.needs_input_grad[1] else None
+        return (None, gx) + (None,) * (len(ctx.needs_input_grad) - 2)

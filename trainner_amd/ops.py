@@ -1285,6 +1285,21 @@ def freqsep_high_bwd(g, o, layout, taps9, gx, gscale=None, accumulate=False):
                                               gx.data_ptr(), int(accumulate), hip.stream()), "freqsep_high_bwd")
 
 
+# Gram matrix of an activation view and its gradient (csrc/gram.hip).  Always on the fp32 activations and in the fp32 arithmetic of
+# TNR_MMA (FP32_MMA), also under `use_amp`: stricter than the reference, whose autocast runs the bmm in half precision.
+def gram_fwd(x, scale, G):
+    lib, dev = hip.load(), x.buf.device
+    nbytes = lib.tnr_gram_workspace_bytes(x.N, x.H, x.W, x.C)
+    ws = WS.get("gram@%x" % hip.stream(), nbytes, dev)
+    hip.check(lib.tnr_gram_fwd(x.c(), x.N, x.H, x.W, x.C, scale, FP32_MMA, G.data_ptr(), ws.data_ptr(), ws.numel() * 8, hip.stream()),
+              "gram_fwd")
+
+
+def gram_bwd(x, S, scale, dx, accumulate=False):
+    hip.check(hip.load().tnr_gram_bwd(x.c(), S.data_ptr(), x.N, x.H, x.W, x.C, scale, FP32_MMA, dx.c(), int(accumulate), hip.stream()),
+              "gram_bwd")
+
+
 def ragan_phase_a(pf, pr, sums):
     hip.check(hip.load().tnr_ragan_phase_a(pf.data_ptr(), pr.data_ptr(), pf.numel(), sums.data_ptr(), _reduce_ws(pf.device).data_ptr(), hip.stream()), "ragan_a")
 
