@@ -167,6 +167,29 @@ def test_dense_block_policy(mma_mode, monkeypatch):
     assert ops.chain_error_flag() == 0
 
 
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("shape", [(1, 8, 32), (1, 10, 20)])
+def test_plan_names_the_form_the_image_caches_show(shape, split, mma_mode, monkeypatch):
+    """ops.dense_block_plan against what ops.dense_block then leaves on the block's packer: "split" = a four-stage sweep image plus the
+    last stage's transform-domain stream, "sweep" = a five-stage sweep image alone, "chain" (the fp32 matrix core) = no sweep image."""
+    from trainner_amd import hip, ops
+    from tools.probes.sweep_check import block
+    _, _, st = block(*shape, seed=7, grad_shape=False)("layers")
+    monkeypatch.setattr(ops, "DENSE_SPLIT", split)
+    form, why = ops.dense_block_plan(st)
+    assert why is None and form == ("chain" if ops.MMA != hip.MMA_BF16X3 else "split" if split else "sweep")
+    owner = st[0]["wp"].owner
+    owner.__dict__.pop("_sweep_images", None)
+    owner.__dict__.pop("_wq_images", None)
+    ops.dense_block(st)
+    torch.cuda.synchronize()
+    sweeps = sorted(len(k) for k in owner.__dict__.get("_sweep_images", {}))
+    wino = [k for k in owner.__dict__.get("_wq_images", {}) if isinstance(k, tuple) and k[0] == "wino"]
+    assert sweeps == {"split": [4], "sweep": [5], "chain": []}[form]
+    assert wino == ([("wino", st[4]["wp"].t.data_ptr())] if form == "split" else [])
+    assert ops.chain_error_flag() == 0
+
+
 def test_dense_split_switch_reads_the_environment():
     """TNR_DENSE_SPLIT=0 turns the form off for a process (a fresh interpreter: the switch is read at import)."""
     import os

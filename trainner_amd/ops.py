@@ -319,35 +319,46 @@ SMALL_GEMM = os.environ.get("TNR_SMALL_GEMM", "1") != "0"   # im2col + split-K G
 
 S2_D4 = os.environ.get("TNR_S2_D4", "1") != "0"      # the four-tap layers (4x4 stride 2 and its data-gradient) on the weight-stream machinery too (A/B switch)
 X3_D4 = os.environ.get("TNR_X3_D4", "1") != "0"      # TNR_MMA=bf16x3: 64-cout 3x3 layers take their weights as a pre-split stream (A/B switch)
-_wq_oneoff = {}
+_wq_oneoff = {}                 # weight-stream images of one-off packs (no owning packer): (key, stream) -> [image, None]
+_sweep_images = {}              # sweep images of one-off packs: ((packed-weight pointers), stream) -> [image, None]
+_ONEOFF_IMAGES = {"_wq_images": _wq_oneoff, "_sweep_images": _sweep_images}
 
 
-def _wq_image(lib, d, wp, dev, tag=None):
-    """The pre-split weight stream of a launch (tnr_conv_desc.wq; None: the launch cannot use one).  Kept on the packer that owns the
-    packed weights and rebuilt (one small launch) when that packer has run since -- once per optimiser step, once ever for the VGG.
-    tag: a second stream of the same weights in another order (the pixel-shuffle store's) is cached under its own key."""
-    need = lib.tnr_conv_wq_bytes(C.byref(d))
-    if need <= 0:
-        return None
-    owner = wp.owner
-    cache, gen = (_wq_oneoff, None) if owner is None else (owner.__dict__.setdefault("_wq_images", {}), owner.gen)
-    # one-off packs (no owning packer): an image per (packed weights, stream) -- it is re-packed on every call on the CURRENT stream,
-    # so two streams must not share one -- and at most 64 of them (least recently used out: the addresses change as tensors come and go)
-    key = wp.t.data_ptr() if owner is not None else (wp.t.data_ptr(), hip.stream())
-    if tag is not None:
-        key = (tag, key)
+def _stream_image(owner, attr, key, need, dev, pack):
+    """The cache of every weight image derived from packed weights: -> ([image, generation], True if this call allocated it).
+    owner: the packer whose run() rewrites those weights.  The image lives in owner.__dict__[attr][key] and is re-packed --
+    pack(image pointer, need): one small launch -- when owner.gen has moved: once per optimiser step, once ever for the VGG.
+    owner None (one-off packs): the image lives in the module-level cache of `attr` and is re-packed on EVERY call, on the CURRENT
+    stream -- so it is kept per (key, stream): two streams must not share one -- and at most 64 of them are kept (least recently
+    used out: the addresses change as tensors come and go).  An entry smaller than `need` bytes is replaced by a new one."""
+    if owner is None:
+        cache, gen, key = _ONEOFF_IMAGES[attr], None, (key, hip.stream())
+    else:
+        cache, gen = owner.__dict__.setdefault(attr, {}), owner.gen
     ent = cache.get(key)
     if owner is None and ent is not None:
         cache[key] = cache.pop(key)          # most recently used last
-    if ent is None or ent[0].numel() * 4 < need:
+    fresh = ent is None or ent[0].numel() * 4 < need
+    if fresh:
         ent = cache[key] = [torch.empty(need // 4, dtype=torch.float32, device=dev), None]
         if owner is None:
             while len(cache) > 64:
                 cache.pop(next(iter(cache)))
     if gen is None or ent[1] != gen:
-        hip.check(lib.tnr_conv_wq_pack(C.byref(d), ent[0].data_ptr(), need, hip.stream()), "conv_wq_pack")
+        pack(ent[0].data_ptr(), need)
         ent[1] = gen
-    return ent[0]
+    return ent, fresh
+
+
+def _wq_image(lib, d, wp, dev, tag=None):
+    """The pre-split weight stream of a launch (tnr_conv_desc.wq; None: the launch cannot use one).
+    tag: a second stream of the same weights in another order (the pixel-shuffle store's) is cached under its own key."""
+    need = lib.tnr_conv_wq_bytes(C.byref(d))
+    if need <= 0:
+        return None
+    key = wp.t.data_ptr() if tag is None else (tag, wp.t.data_ptr())
+    return _stream_image(wp.owner, "_wq_images", key, need, dev,
+                         lambda img, nb: hip.check(lib.tnr_conv_wq_pack(C.byref(d), img, nb, hip.stream()), "conv_wq_pack"))[0][0]
 
 
 # TNR_MMA=bf16x3: 64-cout 3x3 layers in the Winograd F(2x2, 3x3) form (csrc/conv_wino.hip): 2.25 x fewer matrix-core instructions for the
@@ -364,25 +375,12 @@ WINO_MIN_PIXELS = int(os.environ.get("TNR_WINO_MIN_PIXELS", "4096"))
 
 def _wino_image(lib, d, wp, dev):
     """The transform-domain weight stream of a launch (tnr_conv_desc.wq with wq_form = 1; None: the launch cannot run in the Winograd
-    form).  Cached and refreshed like _wq_image: per owning packer and its generation, or per (weights, stream) for one-off packs."""
+    form).  Shares the dictionaries of _wq_image under a ("wino", weights) key."""
     need = lib.tnr_conv_wino_bytes(C.byref(d))
     if need <= 0:
         return None
-    owner = wp.owner
-    cache, gen = (_wq_oneoff, None) if owner is None else (owner.__dict__.setdefault("_wq_images", {}), owner.gen)
-    key = ("wino", wp.t.data_ptr()) if owner is not None else ("wino", wp.t.data_ptr(), hip.stream())
-    ent = cache.get(key)
-    if owner is None and ent is not None:
-        cache[key] = cache.pop(key)
-    if ent is None or ent[0].numel() * 4 < need:
-        ent = cache[key] = [torch.empty(need // 4, dtype=torch.float32, device=dev), None]
-        if owner is None:
-            while len(cache) > 64:
-                cache.pop(next(iter(cache)))
-    if gen is None or ent[1] != gen:
-        hip.check(lib.tnr_conv_wino_pack(C.byref(d), ent[0].data_ptr(), need, hip.stream()), "conv_wino_pack")
-        ent[1] = gen
-    return ent[0]
+    return _stream_image(wp.owner, "_wq_images", ("wino", wp.t.data_ptr()), need, dev,
+                         lambda img, nb: hip.check(lib.tnr_conv_wino_pack(C.byref(d), img, nb, hip.stream()), "conv_wino_pack"))[0][0]
 
 
 SHUFFLE_FOLD = os.environ.get("TNR_SHUFFLE_FOLD", "1") != "0"      # nn.PixelShuffle(2) folded into the convolution's store (A/B switch)
@@ -448,27 +446,124 @@ def conv(x, wp, y, mode=CONV_3x3, wino=None, **epi):
 
 
 CHAIN_MAX = 6
-CHAIN_X3 = os.environ.get("TNR_CHAIN_X3", "1") == "1"   # TNR_MMA=bf16x3 also inside tnr_conv_chain (A/B switch)
-CONV_CHAIN = os.environ.get("TNR_CONV_CHAIN", "1") != "0"     # 0: one launch per layer (A/B switch)
-CONV_SWEEP = os.environ.get("TNR_CONV_SWEEP", "1") != "0"     # TNR_MMA=bf16x3: dense blocks through tnr_conv_sweep (0: tnr_conv_chain; A/B switch)
-COLLECTIVES_IN_FLIGHT = False   # True (dp.py) from the first gradient bucket handed to RCCL on the side stream until the compute
-                                # stream has waited for all of them: a chain launch needs every workgroup of its grid
-                                # co-resident, which RCCL kernels sharing the CUs could delay -> one launch per layer meanwhile
+# The process switches of the dense-block forms (A/B switches: each turns ONE thing off or on).  Which form a block runs in is decided
+# by dense_block_plan below and nowhere else; DESIGN.md 3.2 has the table.
+CONV_CHAIN = os.environ.get("TNR_CONV_CHAIN", "1") != "0"     # 0: one launch per layer
+CONV_SWEEP = os.environ.get("TNR_CONV_SWEEP", "1") != "0"     # 0: tnr_conv_chain where tnr_conv_sweep would run
+CHAIN_X3 = os.environ.get("TNR_CHAIN_X3", "1") == "1"   # 0: TNR_MMA=bf16x3 launches demote to the fp32 matrix core inside tnr_conv_chain
+AMP_SWEEP = os.environ.get("TNR_AMP_SWEEP", "1") != "0"      # 0: use_amp (bf16 operands) keeps tnr_conv_chain instead of the sweep's bf16-operand form
+SWEEP_DISPENSED = os.environ.get("TNR_SWEEP_WAVES", "4") != "8"      # the four-wave forms take their tiles from an atomic counter (conv_sweep.hip)
 # TNR_CHAIN_WITH_COLLECTIVES=1: keep the one-launch forms while gradient buckets are on the wire.  Measured next to a 4 x 64 MB RCCL
 # all-reduce on a side stream (1-rank group, tools/chain_stress.py --rccl, profiles/r03j): bit-identical results, no wait ever timed out,
 # +0.10 ms per dense-block launch (sweep 0.61 -> 0.71 ms, chain 1.01 -> 1.14 ms).  Off by default: with N > 1 ranks an RCCL kernel waits
 # for its peers while it holds CUs the launch wants all of -- never exercised on hardware here.
 CHAIN_WITH_COLLECTIVES = os.environ.get("TNR_CHAIN_WITH_COLLECTIVES", "0") == "1"
-AMP_SWEEP = os.environ.get("TNR_AMP_SWEEP", "1") != "0"      # use_amp (bf16 operands): dense blocks through the sweep's bf16-operand form (0: tnr_conv_chain; A/B switch)
-SWEEP_DISPENSED = os.environ.get("TNR_SWEEP_WAVES", "4") != "8"      # the four-wave forms take their tiles from an atomic counter (conv_sweep.hip)
+# Per-box calibration of the bf16x3 sweep against five per-layer launches (bit-identical results either way).  The sweep hands tiles over
+# between workgroups through system-coherent stores / loads and agent-scope progress words: fabric traffic that never touches L2.  On two
+# of ~25 boxes met in round 5 that path was slow -- the sweep alone ran 1.6 x slower (935-941 vs 587-606 us per launch at batch 16), every
+# other kernel at its usual rate -- while the per-layer path (plain loads and stores, 686 us on a normal box) does not
+# use it.  calibrate_dense_block_form times both forms ONCE, at model set-up, on a scratch block of the TRAINING shape (3 launches each,
+# ~10 ms; never from inside a forward, whose first full-size call could be a validation or tiled-inference shape): "layers" if the sweep
+# is more than 10 % slower.  Data-parallel ranks agree on ONE form (a rank that kept a slow sweep would be the step's straggler); every
+# rank's own measurement is kept in SWEEP_AUTO_STATE["per_rank"] (bench.py prints it).  TNR_SWEEP_AUTO=0: the agreed form is ignored.
+SWEEP_AUTO = os.environ.get("TNR_SWEEP_AUTO", "1") != "0"
+SWEEP_AUTO_STATE = {"choice": None, "sweep_us": None, "layers_us": None}     # choice: None (not calibrated) | "sweep" | "layers"
+# The split form: a block's 64-wide last stage -- 46 % of its multiply-adds -- as a Winograd F(2x2, 3x3) launch (2.25 x fewer matrix
+# instructions; conv_wino.hip) behind a FOUR-stage sweep.  x1 .. x4 stay bit-identical to conv_chain's; the block output carries the Winograd
+# form's error (<= 3 x the fp32 matrix core's against fp64, as everywhere that form runs) and is deterministic.  The five-stage sweep's time is
+# set by the matrix core's dynamic energy, so the instructions removed are what pays.  Measured: DESIGN.md 3.2.
+DENSE_SPLIT = os.environ.get("TNR_DENSE_SPLIT", "1") != "0"
+_SWEEP_FORM_DMA = os.environ.get("TNR_SWEEP_FORM", "")[:2] == "dm"      # (the four-stage plan exists in the direct four-wave form only)
+COLLECTIVES_IN_FLIGHT = False   # True (dp.py) from the first gradient bucket handed to RCCL on the side stream until the compute stream has waited for all
 COUNTERS = {"one_launch_next_to_collectives": 0, "per_layer_next_to_collectives": 0}      # dense blocks launched while gradient buckets were in flight
+_cu_counts = {}
+_LIVE = object()                # dense_block_plan: "read the module's state now" (the default of every what-if argument)
+
+
+def _cus(dev):
+    if dev not in _cu_counts:
+        _cu_counts[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return _cu_counts[dev]
+
+
+def _on_device(buf):
+    return buf.is_cuda
+
+
+def _crowded(in_flight):
+    return in_flight and not CHAIN_WITH_COLLECTIVES
+
+
+def _chain_mma(mma):          # the arithmetic a one-launch form runs a launch of arithmetic `mma` in
+    return hip.MMA_F32 if mma == hip.MMA_BF16X3 and not CHAIN_X3 else mma
+
+
+def _eligible(stages):          # the shapes the one-launch kernels take
+    return all(st.get("mode", CONV_3x3) == CONV_3x3 and st["y"].C % 32 == 0 and st["wp"].KoutP == st["y"].C for st in stages)
+
+
+def _split_shape(stages):
+    """The stricter shape rule of the split form: a function of the block's PER-IMAGE grid and channel counts, never of the batch size
+    (data-parallel shards of one global batch pick the same form as one process would)."""
+    x0 = stages[0]["x"]
+    if not all(st.get("mode", CONV_3x3) == CONV_3x3 and not st.get("reflect") and st["wp"].KoutP == st["y"].C and st["wp"].KinP == st["x"].C for st in stages) \
+            or stages[4]["y"].C != 64 or any(st["y"].C != 32 for st in stages[:4]) or x0.C % 16 or x0.C < 32 or stages[4]["x"].C != x0.C + 128:
+        return False
+    # the sweep keeps an image's 8 x 32 tiles co-resident (one workgroup per CU); the Winograd kernel wants an 8 x 8 grid at least
+    return x0.H >= 8 and x0.W >= 8 and -(-x0.W // 32) * -(-x0.H // 8) <= _cus(x0.buf.device)
+
+
+def dense_block_plan(stages, crowded=_LIVE, mma=_LIVE, choice=_LIVE, sweepable=True):
+    """The form the dependent convolutions `stages` (1 .. CHAIN_MAX of them) run in right now -> (form, reason):
+      ("layers", why)  one launch per stage.  why = "switch": TNR_CONV_CHAIN=0.  "shape": a stage the one-launch kernels do not take (_eligible).
+                       "calibrated": the calibration (this box's or another rank's) chose per-layer launches -- heeded where the sweep would run, in
+                       the bf16x3 arithmetic, on the device, unless TNR_SWEEP_AUTO=0.  "crowded": gradient buckets are on the wire (unless
+                       TNR_CHAIN_WITH_COLLECTIVES=1) and the form that would run needs its whole grid co-resident, which RCCL's kernels on the same
+                       CUs could delay: tnr_conv_chain and the eight-wave sweep.  The four-wave sweep DISPENSES its tiles in order (a waited-for tile
+                       was either taken by a running workgroup or is the next to be dispensed): stage s of tile T reads stage s - 1 of T + tiles_x + 1,
+                       so 4 (tiles_x + 1) + 1 resident workgroups guarantee progress (21 on the 128-wide trunk, never more than one image's tiles).
+      ("chain", None)  tnr_conv_chain: every eligible list the sweep does not exist for.
+      ("sweep", None)  tnr_conv_sweep: five stages in the bf16x3 arithmetic (unless TNR_CHAIN_X3=0) or under bf16 operands (unless TNR_AMP_SWEEP=0),
+                       four stages in bf16x3 (a split block's first four); TNR_CONV_SWEEP=0: never.
+      ("split", None)  dense_block only (conv_chain reads it as "sweep"): the four-stage sweep, then the last stage as a Winograd launch.  Five stages of
+                       the dispensed bf16x3 sweep on the device, nothing crowded, _split_shape, unless TNR_DENSE_SPLIT=0 or the sweep's DMA form is selected.
+    Everything is read at call time; the keyword arguments ask a what-if instead: crowded = buckets in flight, mma = the arithmetic, choice = the
+    calibrated form, sweepable=False = tnr_conv_sweep declined this block; stages None = a well-shaped five-stage block on the device."""
+    n = 5 if stages is None else len(stages)
+    mma = _chain_mma(MMA if mma is _LIVE else mma)
+    x3 = mma == hip.MMA_BF16X3
+    if not CONV_CHAIN:
+        return "layers", "switch"
+    if stages is not None and not _eligible(stages):
+        return "layers", "shape"
+    on_device = stages is None or _on_device(stages[0]["x"].buf)
+    sweep = sweepable and CONV_SWEEP and ((n in (4, 5) and x3) or (n == 5 and mma == hip.MMA_BF16 and AMP_SWEEP))
+    if sweep and x3 and on_device and SWEEP_AUTO and (SWEEP_AUTO_STATE["choice"] if choice is _LIVE else choice) == "layers":
+        return "layers", "calibrated"
+    crowded = _crowded(COLLECTIVES_IN_FLIGHT if crowded is _LIVE else crowded)
+    dispensed = sweep and SWEEP_DISPENSED
+    if crowded and not dispensed:
+        return "layers", "crowded"
+    if not sweep:
+        return "chain", None
+    if DENSE_SPLIT and dispensed and x3 and n == 5 and on_device and not crowded and not _SWEEP_FORM_DMA and stages is not None and _split_shape(stages):
+        return "split", None
+    return "sweep", None
+
+
+def dense_split_applies(stages):
+    return dense_block_plan(stages)[0] == "split"
+
+
+def dense_block_form_applies(stages):
+    """Is `stages` a block the calibration decides about: would it heed a calibrated "layers" in the step's fp32 arithmetic?"""
+    return len(stages) == 5 and dense_block_plan(stages, mma=FP32_MMA, choice="layers") == ("layers", "calibrated")
 
 
 def dense_blocks_overlap_collectives():
-    """True when the dense blocks stay one launch each next to in-flight gradient buckets in the CURRENT arithmetic (the dispensed
-    sweep of TNR_MMA_BF16X3, or TNR_CHAIN_WITH_COLLECTIVES=1): the generator's all-reduce can then overlap its backward for free."""
-    return CHAIN_WITH_COLLECTIVES or (CONV_CHAIN and CONV_SWEEP and SWEEP_DISPENSED and
-                                      ((CHAIN_X3 and MMA == hip.MMA_BF16X3) or (AMP_SWEEP and MMA == hip.MMA_BF16)))
+    """True when the dense blocks stay one launch each next to in-flight gradient buckets in the CURRENT arithmetic: the generator's
+    all-reduce can then overlap its backward for free."""
+    return not _crowded(True) or dense_block_plan(None, crowded=True, choice=None)[0] != "layers"
 
 
 def g_buckets_leave_in_backward():
@@ -500,62 +595,38 @@ def _repack_sweep_images(owner):
 
 
 _chain_epoch = {}
-_sweep_images = {}              # sweep images of one-off packs (no owning packer): (packed-weight pointers) -> [image, None]
 
 
 def _sweep_image(lib, descs, n, stages, dev):
-    """The pre-split weight stream of a dense block for tnr_conv_sweep (None: not sweepable).  Kept on the packer that owns the
-    block's packed weights and rebuilt (one small launch) when that packer has run since -- once per optimiser step."""
+    """The pre-split weight stream of a dense block for tnr_conv_sweep (None: not sweepable), keyed by the stages' packed weights."""
     need = lib.tnr_conv_sweep_image_bytes(descs, n)
     if need <= 0:
         return None
-    owner = stages[0]["wp"].owner
-    if owner is None or any(st["wp"].owner is not owner for st in stages):
-        owner = None
-        cache, gen = _sweep_images, None               # one-off packs: rebuilt on every call
-    else:
-        cache = owner.__dict__.setdefault("_sweep_images", {})
-        gen = owner.gen
-    key = tuple(st["wp"].t.data_ptr() for st in stages) + (() if owner is not None else (hip.stream(),))
-    ent = cache.get(key)
-    if owner is None and ent is not None:
-        cache[key] = cache.pop(key)          # one-off packs: per stream, least recently used out (see _wq_image)
-    if ent is None or ent[0].numel() * 4 < need:
-        ent = cache[key] = [torch.empty(need // 4, dtype=torch.float32, device=dev), None]
-        if owner is None:
-            while len(cache) > 64:
-                cache.pop(next(iter(cache)))
-    if gen is None or ent[1] != gen:
-        hip.check(lib.tnr_conv_sweep_pack(descs, n, ent[0].data_ptr(), need, hip.stream()), "conv_sweep_pack")
-        if owner is not None and SWEEP_PACK_BATCH and ent[1] is None:
-            # first build of this block's image: from the owner's next run() on it is rebuilt with all the others in one launch
-            item = hip.SweepPackItem()
-            hip.check(lib.tnr_conv_sweep_pack_item(descs, n, ent[0].data_ptr(), need, C.byref(item)), "conv_sweep_pack_item")
-            b = owner.__dict__.setdefault("_sweep_batch", {"items": [], "ents": [], "table": None, "max_units": 0})
-            b["items"].append(item)
-            b["ents"].append(ent)
-            b["table"] = None
-            b["max_units"] = max(b["max_units"], item.units)
-        ent[1] = gen
+    owner = stages[0]["wp"].owner if all(st["wp"].owner is stages[0]["wp"].owner for st in stages) else None
+    ent, fresh = _stream_image(owner, "_sweep_images", tuple(st["wp"].t.data_ptr() for st in stages), need, dev,
+                               lambda img, nb: hip.check(lib.tnr_conv_sweep_pack(descs, n, img, nb, hip.stream()), "conv_sweep_pack"))
+    if fresh and owner is not None and SWEEP_PACK_BATCH:
+        # first build of this block's image: from the owner's next run() on it is rebuilt with all the others in one launch
+        item = hip.SweepPackItem()
+        hip.check(lib.tnr_conv_sweep_pack_item(descs, n, ent[0].data_ptr(), need, C.byref(item)), "conv_sweep_pack_item")
+        b = owner.__dict__.setdefault("_sweep_batch", {"items": [], "ents": [], "table": None, "max_units": 0})
+        b["items"].append(item)
+        b["ents"].append(ent)
+        b["table"] = None
+        b["max_units"] = max(b["max_units"], item.units)
     return ent[0]
-
-
-# Per-box choice between the one-launch dense block and five per-layer launches in TNR_MMA_BF16X3 (bit-identical results either way).
-# The sweep hands tiles over between workgroups through system-coherent stores / loads and agent-scope progress words: fabric traffic
-# that never touches L2.  On two of ~25 boxes met in round 5 that path was slow -- the sweep alone ran 1.6 x slower (935-941 vs 587-606 us
-# per launch at batch 16), every other kernel at its usual rate (DESIGN.md 3.2) -- while the per-layer path (plain loads and stores,
-# 686 us on a normal box) does not use it.  The choice is made EXPLICITLY, once, when a training model is set up
-# (`calibrate_dense_block_form`, called by SRModel with a scratch block of the TRAINING shape -- never from inside a forward, whose first
-# full-size call could be a validation or tiled-inference shape): both forms are timed (3 launches each, ~10 ms) and the per-layer path
-# is taken if the sweep is more than 10 % SLOWER than it.  Data-parallel ranks agree on ONE form (all-reduce MAX: if any rank's sweep is
-# slow every rank runs per-layer launches -- a rank that kept the slow sweep would be the step's straggler) and every rank's own
-# measurement is kept in SWEEP_AUTO_STATE["per_rank"] (bench.py prints it).  Not calibrated (choice None): the sweep.  TNR_SWEEP_AUTO=0: off.
-SWEEP_AUTO = os.environ.get("TNR_SWEEP_AUTO", "1") != "0"
-SWEEP_AUTO_STATE = {"choice": None, "sweep_us": None, "layers_us": None}     # choice: None (not calibrated) | "sweep" | "layers"
 
 
 def _stage_views(st):
     return [st[k] for k in ("x", "y", "r1", "r2", "mask") if st.get(k) is not None]
+
+
+def _per_layer(stages, why=None):
+    """One launch per stage, in the direct kernels: bit-identical to the one-launch forms (never the Winograd form)."""
+    if why == "crowded":
+        COUNTERS["per_layer_next_to_collectives"] += 1
+    for st in stages:
+        conv(wino=False, **{k: v for k, v in st.items() if k != "fresh_from"})
 
 
 def _calibrate_dense_block(stages):
@@ -584,12 +655,8 @@ def _calibrate_dense_block(stages):
             torch.cuda.synchronize()
             return 1e3 * a.elapsed_time(b) / 3.0
 
-        def layers():
-            for st in stages:
-                conv(wino=False, **{k: v for k, v in st.items() if k != "fresh_from"})      # (the direct kernels: bit-identical to the one-launch forms)
-
         SWEEP_AUTO_STATE["choice"] = "sweep"                # (the timed calls below go through conv_chain itself)
-        t_sweep, t_layers = timed(lambda: conv_chain(stages)), timed(layers)
+        t_sweep, t_layers = timed(lambda: conv_chain(stages)), timed(lambda: _per_layer(stages))
         t_sweep = min(t_sweep, timed(lambda: conv_chain(stages)))          # (the clock may still be ramping at a process's first launches)
         prev = "layers" if t_sweep > 1.10 * t_layers else "sweep"
         SWEEP_AUTO_STATE.update(sweep_us=round(t_sweep, 1), layers_us=round(t_layers, 1))
@@ -598,14 +665,8 @@ def _calibrate_dense_block(stages):
         PROFILE = prof
 
 
-def dense_block_form_applies(stages):
-    return (SWEEP_AUTO and CONV_CHAIN and CONV_SWEEP and CHAIN_X3 and len(stages) == 5 and FP32_MMA == hip.MMA_BF16X3 and
-            stages[0]["x"].buf.is_cuda and
-            all(st.get("mode", CONV_3x3) == CONV_3x3 and st["y"].C % 32 == 0 and st["wp"].KoutP == st["y"].C for st in stages))
-
-
 def calibrate_dense_block_form(stages, dp=None):
-    """The explicit per-box calibration (see above).  stages: a dense block over SCRATCH buffers of the training shape (None: nothing to
+    """The explicit per-box calibration (see SWEEP_AUTO).  stages: a dense block over SCRATCH buffers of the training shape (None: nothing to
     time here -- a CPU stand-in run -- but the ranks still exchange their records).  dp: the
     data-parallel group -- every rank must call this at the same point (two small collectives).  Returns SWEEP_AUTO_STATE."""
     applies = bool(stages) and dense_block_form_applies(stages)
@@ -637,43 +698,22 @@ def calibrate_dense_block_form(stages, dp=None):
 
 
 def conv_chain(stages):
-    """Dependent 3x3 convolutions over one pixel grid in one launch (tnr_conv_chain).  stages: dicts with the
-    arguments of conv() (x, wp, y, bias, act, ..., mask) plus fresh_from: first input channel produced by the
-    previous stage of this chain (None for the first stage).  Same results as calling conv() per stage.
-    In TNR_MMA_BF16X3 a residual dense block (or its gradient mirror) goes through tnr_conv_sweep instead: every input channel
-    chunk read once per phase for all the stages that consume it, weights streamed pre-split (csrc/conv_sweep.hip)."""
+    """Dependent 3x3 convolutions over one pixel grid, in one launch where dense_block_plan allows it.  stages: dicts with the arguments of
+    conv() (x, wp, y, bias, act, ..., mask) plus fresh_from: first input channel produced by the previous stage of this chain (None for the
+    first stage).  Same results as calling conv() per stage.  tnr_conv_chain is the general one-launch form; tnr_conv_sweep reads every input
+    channel chunk once per phase for all the stages that consume it and streams the weights pre-split (csrc/conv_sweep.hip)."""
     n = len(stages)
     assert 1 <= n <= CHAIN_MAX
-    eligible = all(st.get("mode", CONV_3x3) == CONV_3x3 and st["y"].C % 32 == 0 and st["wp"].KoutP == st["y"].C for st in stages)
-    # gradient buckets on the wire: tnr_conv_chain (and the eight-wave sweep) need their whole grid co-resident, which RCCL's
-    # kernels on the same CUs could delay -> one launch per layer meanwhile.  The four-wave sweep DISPENSES its tiles in order (a
-    # waited-for tile was either taken by a running workgroup or is the next to be dispensed).  Stage s of tile T reads stage s - 1 of
-    # T + tiles_x + 1, so T finishes its five stages once tiles up to T + 4 (tiles_x + 1) are held: 4 (tiles_x + 1) + 1 resident
-    # workgroups guarantee progress (21 on the 128-wide trunk, never more than the tiles of one image): it may
-    # stay one launch -- opt-in (TNR_DP_OVERLAP_G=1, models/sr_model.py) until a multi-GPU run has exercised it.
-    crowded = COLLECTIVES_IN_FLIGHT and not CHAIN_WITH_COLLECTIVES
-    # (n == 4: a block's first four stages -- the four-stage plan of the sweep, bf16x3 only; dense_block runs the fifth on its own)
-    sweep_ok = CONV_SWEEP and ((n in (4, 5) and MMA == hip.MMA_BF16X3 and CHAIN_X3) or (n == 5 and MMA == hip.MMA_BF16 and AMP_SWEEP))
-    auto = SWEEP_AUTO and CONV_CHAIN and eligible and sweep_ok and MMA == hip.MMA_BF16X3 and stages[0]["x"].buf.is_cuda
-    if auto and SWEEP_AUTO_STATE["choice"] == "layers":      # (calibrate_dense_block_form chose it at model set-up: never timed here)
-        for st in stages:
-            conv(wino=False, **{k: v for k, v in st.items() if k != "fresh_from"})      # (the direct kernels: bit-identical to the one-launch forms)
-        return
-    if not CONV_CHAIN or not eligible or (crowded and not (sweep_ok and SWEEP_DISPENSED)):
-        if crowded and CONV_CHAIN and eligible:
-            COUNTERS["per_layer_next_to_collectives"] += 1
-        for st in stages:
-            conv(wino=False, **{k: v for k, v in st.items() if k != "fresh_from"})      # (the direct kernels: bit-identical to the one-launch forms)
-        return
+    form, why = dense_block_plan(stages)
+    if form == "layers":
+        return _per_layer(stages, why)
     lib = hip.load()
     descs = (ConvDesc * n)()
     fresh = (C.c_int32 * n)()
     flops = 0.0
     for i, st in enumerate(stages):
-        kw = {k: v for k, v in st.items() if k != "fresh_from"}
-        _conv_desc(descs[i], **kw)
-        if descs[i].mma == hip.MMA_BF16X3 and not CHAIN_X3:
-            descs[i].mma = hip.MMA_F32
+        _conv_desc(descs[i], **{k: v for k, v in st.items() if k != "fresh_from"})
+        descs[i].mma = _chain_mma(descs[i].mma)
         ff = st.get("fresh_from")
         fresh[i] = -1 if ff is None else ff
         flops += 2.0 * st["y"].pixels * 9 * min(st["x"].C, st["wp"].KinP) * st["y"].C
@@ -690,14 +730,12 @@ def conv_chain(stages):
     if _chain_epoch[key] > 0x0FFFFFF0:                 # epoch wrap: stale counters would compare as already satisfied
         fill(ws[:-1].view(torch.float32), 0.0)         # (stream-ordered after every earlier launch on this stream)
         _chain_epoch[key] = 1
-    image = None
-    if CONV_SWEEP and ((n in (4, 5) and descs[0].mma == hip.MMA_BF16X3) or (n == 5 and descs[0].mma == hip.MMA_BF16 and AMP_SWEEP)):
-        image = _sweep_image(lib, descs, n, stages, dev)
-    if crowded and image is None:                      # (a block the sweep does not cover: shapes, tiles per image)
-        COUNTERS["per_layer_next_to_collectives"] += 1
-        for st in stages:
-            conv(wino=False, **{k: v for k, v in st.items() if k != "fresh_from"})      # (the direct kernels: bit-identical to the one-launch forms)
-        return
+    image = _sweep_image(lib, descs, n, stages, dev) if form != "chain" else None
+    if form != "chain" and image is None:
+        # the one late fallback: a block the sweep does not cover after all (shapes, tiles per image) -> tnr_conv_chain, or per layer
+        form, why = dense_block_plan(stages, sweepable=False)
+        if form == "layers":
+            return _per_layer(stages, why)
     if COLLECTIVES_IN_FLIGHT:
         COUNTERS["one_launch_next_to_collectives"] += 1
     t0 = PROFILE.begin() if PROFILE is not None else None
@@ -710,48 +748,9 @@ def conv_chain(stages):
         PROFILE.end("conv_chain", flops, t0, (x0.C, yl.C, yl.H, stages[0]["wp"].kind))
 
 
-# TNR_MMA=bf16x3: a dense block as a FOUR-stage sweep (conv1 .. conv4, or stages 1 .. 4 of the gradient mirror: conv_chain(stages[:4]))
-# plus its 64-wide last stage -- 46 % of the block's multiply-adds -- as a Winograd F(2x2, 3x3) launch (2.25 x fewer matrix
-# instructions; conv_wino.hip).  x1 .. x4 stay bit-identical to conv_chain's; the block output carries the Winograd form's error (<= 3 x
-# the fp32 matrix core's against fp64, as everywhere that form runs) and is deterministic.  The five-stage sweep's time is set by the
-# matrix core's dynamic energy, so the instructions removed are what pays.  Measured: DESIGN.md 3.2.  0: conv_chain(stages).
-DENSE_SPLIT = os.environ.get("TNR_DENSE_SPLIT", "1") != "0"
-_SWEEP_FORM_DMA = os.environ.get("TNR_SWEEP_FORM", "")[:2] == "dm"
-_cu_counts = {}
-
-
-def _cus(dev):
-    n = _cu_counts.get(dev)
-    if n is None:
-        n = _cu_counts[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
-    return n
-
-
-def dense_split_applies(stages):
-    """Does dense_block run `stages` in the split form?  A function of the arithmetic, the process switches, the agreed dense-block
-    form and the block's PER-IMAGE grid and channel counts -- never of the batch size (data-parallel shards of one global batch pick
-    the same form as one process would)."""
-    if not (DENSE_SPLIT and CONV_CHAIN and CONV_SWEEP and SWEEP_DISPENSED and CHAIN_X3 and MMA == hip.MMA_BF16X3 and len(stages) == 5):
-        return False
-    x0, yl = stages[0]["x"], stages[4]["y"]
-    if not x0.buf.is_cuda or _SWEEP_FORM_DMA:          # (the four-stage plan exists in the direct four-wave form only)
-        return False
-    if SWEEP_AUTO and SWEEP_AUTO_STATE["choice"] == "layers":
-        return False
-    if COLLECTIVES_IN_FLIGHT and not CHAIN_WITH_COLLECTIVES:
-        return False
-    if not all(st.get("mode", CONV_3x3) == CONV_3x3 and not st.get("reflect") and st["wp"].KoutP == st["y"].C and st["wp"].KinP == st["x"].C
-               for st in stages):
-        return False
-    if yl.C != 64 or any(st["y"].C != 32 for st in stages[:4]) or x0.C % 16 or x0.C < 32 or stages[4]["x"].C != x0.C + 128:
-        return False
-    # the sweep keeps an image's 8 x 32 tiles co-resident (one workgroup per CU); the Winograd kernel wants an 8 x 8 grid at least
-    return x0.H >= 8 and x0.W >= 8 and -(-x0.W // 32) * -(-x0.H // 8) <= _cus(x0.buf.device)
-
-
 def dense_block(stages):
     """A residual dense block's five convolutions (or the five of its gradient mirror): conv_chain(stages), or -- where
-    dense_split_applies -- the four-stage sweep followed by the last stage in the Winograd form."""
+    dense_block_plan says "split" -- the four-stage sweep followed by the last stage in the Winograd form."""
     if not dense_split_applies(stages):
         return conv_chain(stages)
     last = {k: v for k, v in stages[4].items() if k != "fresh_from"}
