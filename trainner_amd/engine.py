@@ -28,63 +28,47 @@ class ConvOp:
         # deep layers that can meet a tiny spatial extent (discriminator tail): column-layout packings for the
         # im2col + split-K GEMM path (ops.conv_small)
         deep = mod.in_channels * k * k >= 2048 and not ups
-        self.i_fc = packer.add(mod.weight, ops.PACK_COL_FWD) if deep else None
-        self.i_dc = packer.add(mod.weight, ops.PACK_COL_DGRAD3) if (deep and need_dgrad and k == 3) else None
-        self.k, self.stride = k, s
+        i_fc = packer.add(mod.weight, ops.PACK_COL_FWD) if deep else None
+        i_dc = packer.add(mod.weight, ops.PACK_COL_DGRAD3) if (deep and need_dgrad and k == 3) else None
         # <= 4-channel image on either side of a 3x3 layer: taps folded into K (TNR_CONV_3x3_C4)
         img = k == 3 and s == 1 and not ups
-        self.thin = img                 # <= 4 channels on the OUTPUT side of a launch: vector-ALU kernel (conv_thin.hip)
-        self.i_f4 = packer.add(mod.weight, ops.PACK_C4_FWD) if (img and mod.in_channels <= 4) else None
-        self.i_d4 = packer.add(mod.weight, ops.PACK_C4_DGRAD3) if (img and need_dgrad and mod.out_channels <= 4) else None
+        self.thin = img                 # <= 4 channels on one side: vector-ALU kernels (conv_thin.hip)
+        i_f4 = packer.add(mod.weight, ops.PACK_C4_FWD) if (img and mod.in_channels <= 4) else None
+        i_d4 = packer.add(mod.weight, ops.PACK_C4_DGRAD3) if (img and need_dgrad and mod.out_channels <= 4) else None
+        # per direction (False: forward, True: data-gradient): the launch mode and the facts ops.conv_plan decides on
+        cin, cout = mod.in_channels, mod.out_channels
+        self.dirs = {False: (self.mode_f, ops.ConvLayer(k, s, cin, cout, False, ups, direct=self.i_f, c4=i_f4, col=i_fc)),
+                     True: (self.mode_d, ops.ConvLayer(k, s, cin, cout, True, ups, direct=self.i_d, c4=i_d4, col=i_dc))}
 
-    @staticmethod
-    def _image4(v):
-        """The whole 4-channel pixel of an NHWC4 image view (3 channels + the zero pad), or None."""
-        if ops.IMAGE_C4 and v.ctot == 4 and v.coff == 0:
-            return v if v.C == 4 else ops.View(v.buf)
-        return None
-
-    @staticmethod
-    def _plain(epi):
-        """Only bias / alpha: what the vector-ALU thin kernel's epilogue covers."""
-        return all(epi.get(n) is None for n in ("r1", "r2", "mask")) and epi.get("act", ops.ACT_NONE) == ops.ACT_NONE
+    def _run(self, dgrad, x, y, epi):
+        """One launch of this layer in the form ops.conv_plan names."""
+        mode, layer = self.dirs[dgrad]
+        wp = self.packer.get(layer.direct)
+        form = ops.conv_plan(x, wp, y, mode, epi, layer=layer)[0]
+        if form == "thin":
+            ops.conv_thin(x, self.mod.weight, y, bias=None if dgrad else self.mod.bias, alpha=epi.get("alpha", 1.0), dgrad=dgrad)
+        elif form == "c4":          # the whole 4-channel pixel of the NHWC4 image (3 channels + the zero pad)
+            ops.conv(x if x.C == 4 else ops.View(x.buf), self.packer.get(layer.c4), y, mode=ops.CONV_3x3_C4, **epi)
+        elif form == "im2col":
+            ops.conv_small(x, self.packer.get(layer.col), y, layer.k, layer.stride, **epi)
+        else:
+            ops.conv(x, wp, y, mode=mode, **epi)
 
     def fwd(self, x, y, **epi):
-        if self.thin and ops.IMAGE_C4 and self.mod.out_channels <= 4 and y.C <= 4 and self._plain(epi):
-            ops.conv_thin(x, self.mod.weight, y, bias=self.mod.bias, alpha=epi.get("alpha", 1.0))
-            return
-        x4 = self._image4(x) if self.i_f4 is not None else None
-        if x4 is not None:
-            ops.conv(x4, self.packer.get(self.i_f4), y, mode=ops.CONV_3x3_C4, bias=self.mod.bias, **epi)
-            return
-        if self.i_fc is not None and ops.small_gemm_ok(x, y, self.k, self.stride, epi):
-            ops.conv_small(x, self.packer.get(self.i_fc), y, self.k, self.stride, bias=self.mod.bias, **epi)
-            return
-        ops.conv(x, self.packer.get(self.i_f), y, mode=self.mode_f, bias=self.mod.bias, **epi)
+        epi["bias"] = self.mod.bias
+        self._run(False, x, y, epi)
 
     def fwd_shuffle2(self, x, y, **epi):
         """This layer + nn.PixelShuffle(2) in one launch, y = the shuffled tensor (ops.conv_shuffle2); False: not available here."""
-        if self.mode_f != ops.CONV_3x3 or self.mod.out_channels != 4 * y.C:
-            return False
-        return ops.conv_shuffle2(x, self.packer.get(self.i_f), y, bias=self.mod.bias, **epi)
+        return ops.conv_shuffle2(x, self.packer.get(self.i_f), y, layer=self.dirs[False][1], bias=self.mod.bias, **epi)
+
+    def dgrad(self, g, gx, **epi):
+        """gx = conv_transpose(g); for an UP2 layer gx lives in the up-sampled domain."""
+        self._run(True, g, gx, epi)
 
     def fwd_stage(self, x, y, fresh_from=None, **epi):
         """Stage descriptor of this layer's forward for ops.conv_chain."""
         return dict(x=x, wp=self.packer.get(self.i_f), y=y, mode=self.mode_f, bias=self.mod.bias, fresh_from=fresh_from, **epi)
-
-    def dgrad(self, g, gx, **epi):
-        """gx = conv_transpose(g); for an UP2 layer gx lives in the up-sampled domain."""
-        if self.thin and ops.IMAGE_C4 and self.mod.in_channels <= 4 and gx.C <= 4 and self._plain(epi):
-            ops.conv_thin(g, self.mod.weight, gx, alpha=epi.get("alpha", 1.0), dgrad=True)
-            return
-        g4 = self._image4(g) if self.i_d4 is not None else None
-        if g4 is not None:
-            ops.conv(g4, self.packer.get(self.i_d4), gx, mode=ops.CONV_3x3_C4, **epi)
-            return
-        if self.i_dc is not None and ops.small_gemm_ok(g, gx, 3, 1, epi):
-            ops.conv_small(g, self.packer.get(self.i_dc), gx, 3, 1, **epi)
-            return
-        ops.conv(g, self.packer.get(self.i_d), gx, mode=self.mode_d, **epi)
 
     def wgrad_item(self, x, g, alpha=1.0, cin_begin=0, with_bias=True, reflect=False):
         """Descriptor of dW[:, cin_begin : cin_begin + x.C] (+ db) += alpha * (g (x) x) for ops.wgrad_group."""

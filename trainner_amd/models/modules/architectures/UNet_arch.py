@@ -15,7 +15,7 @@ Kernel mapping (all fp32 NHWC): every convolution is the 4x4 stride-2 space-to-d
 data-gradient of that geometry (TNR_DGRAD_4x4_S2) with its [in, out, 4, 4] weight read as a convolution weight [O = in, I = out], its
 input gradient is the forward kernel and its weight gradient the weight-gradient kernel with the roles of the two tensors swapped
 (engine.ConvOp on a shim module).  The 3-channel image sides are zero-extended to 4 channels (weights and buffers).  Layers of <= 4096
-output pixels go through the im2col + split-K GEMM (ops.small_gemm_ok), as in the discriminator's tail.
+output pixels go through the im2col + split-K GEMM (the "im2col" row of ops.conv_plan), as in the discriminator's tail.
 """
 import torch
 import torch.nn as nn

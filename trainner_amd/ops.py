@@ -2,6 +2,7 @@
 
 Nothing here computes with torch; torch only allocates the buffers the kernels read and write.
 """
+import collections
 import ctypes as C
 
 import os
@@ -315,8 +316,6 @@ def gauss_mult(dst, src, noise):
 
 IMAGE_C4 = os.environ.get("TNR_IMAGE_C4", "1") != "0"       # taps-in-K kernel for <= 4-channel image layers (A/B switch)
 SMALL_GEMM = os.environ.get("TNR_SMALL_GEMM", "1") != "0"   # im2col + split-K GEMM for <= 4096-pixel layers (A/B switch)
-
-
 S2_D4 = os.environ.get("TNR_S2_D4", "1") != "0"      # the four-tap layers (4x4 stride 2 and its data-gradient) on the weight-stream machinery too (A/B switch)
 X3_D4 = os.environ.get("TNR_X3_D4", "1") != "0"      # TNR_MMA=bf16x3: 64-cout 3x3 layers take their weights as a pre-split stream (A/B switch)
 _wq_oneoff = {}                 # weight-stream images of one-off packs (no owning packer): (key, stream) -> [image, None]
@@ -381,68 +380,147 @@ def _wino_image(lib, d, wp, dev):
         return None
     return _stream_image(wp.owner, "_wq_images", ("wino", wp.t.data_ptr()), need, dev,
                          lambda img, nb: hip.check(lib.tnr_conv_wino_pack(C.byref(d), img, nb, hip.stream()), "conv_wino_pack"))[0][0]
-
-
 SHUFFLE_FOLD = os.environ.get("TNR_SHUFFLE_FOLD", "1") != "0"      # nn.PixelShuffle(2) folded into the convolution's store (A/B switch)
+_LIVE = object()                # conv_plan / dense_block_plan: "read the module's state now" (the default of every what-if argument)
+# what engine.ConvOp knows about its layer and the direction of a launch; direct / c4 / col: the packer's index of that packing, None where the layer owns none
+ConvLayer = collections.namedtuple("ConvLayer", "k stride cin cout dgrad ups direct c4 col")
+_STREAM_MMA = (hip.MMA_BF16X3, hip.MMA_BF16)
+_FUSED = ("r1", "r2", "mask")
+# mode -> (PROFILE family, taps per output pixel: one of the stride-2 data-gradient sees 4 of the 16)
+_CONV_FAMILY = {CONV_3x3: ("conv_tile_3x3", 9), CONV_3x3_UP2: ("conv_tile_3x3_up2", 9), CONV_4x4_S2: ("conv_tile_4x4s2", 16), DGRAD_4x4_S2: ("conv_tile_dgrad4x4s2", 4),
+                CONV_1x1: ("conv_tile_1x1", 1), CONV_3x3_C4: ("conv_tile_3x3_c4", 9), CONV_7x7_C4: ("conv_tile_7x7_c4", 49)}
 
 
-def conv_shuffle2(x, wp, y, **epi):
-    """conv (nf -> 4 nf, 3x3) + nn.PixelShuffle(2) + the epilogue's activation in ONE launch (block.pixelshuffle_block, block.py:374-387):
-    y is the SHUFFLED tensor [N, 2 H, 2 W, nf]; the [N, H, W, 4 nf] intermediate and the depth-to-space pass do not exist
-    (tnr_conv_desc.shuffle).  Returns False when the launch cannot run that way (fp32-matrix-core arithmetic, shapes the weight-stream
-    kernel does not take): the caller then runs conv + depth_to_space."""
-    if not (SHUFFLE_FOLD and X3_D4 and MMA in (hip.MMA_BF16X3, hip.MMA_BF16) and x.buf.is_cuda):
-        return False
-    assert y.H == 2 * x.H and y.W == 2 * x.W and wp.KoutP == 4 * y.C
-    lib = hip.load()
-    d = ConvDesc()
-    _conv_desc(d, x, wp, y, CONV_3x3, **epi)
-    d.Ho, d.Wo, d.Cout, d.shuffle = x.H, x.W, 4 * y.C, 2
-    d.m_hi = 0
-    img = _wq_image(lib, d, wp, x.buf.device, tag="shuffle2")
-    if img is None:
-        return False
-    d.wq, d.wq_bytes = img.data_ptr(), img.numel() * 4
+def conv_plan(x, wp, y, mode=CONV_3x3, epi=None, shuffle=0, layer=None, wino=None, mma=_LIVE, splitk=True, wino_ok=True, stream_ok=True):
+    """The form ONE convolution runs in right now -> (form, reason).  First matching row wins.  reason: None on the straight path, else why the FIRST
+    better form was passed over: "switch", "arithmetic", "shape", "epilogue", "declined" (the library said no), "forbidden" (the caller's wino=False);
+    two rows carry a word of their own: ("tile", "splitk") and ("wino", "forced").
+    shuffle = 2 (conv + nn.PixelShuffle(2) in one store, y = the shuffled tensor) has one form:
+      ("stream", None)    TNR_SHUFFLE_FOLD and TNR_X3_D4 on, device tensors; bf16x3 or bf16 operands; a 3x3 stride-1 layer, not nearest-x2, of exactly 4 y.C
+                          outputs, no padding rows in its packing (KoutP == 4 y.C), y twice the size of x; tnr_conv_wq_bytes > 0.
+      ("tile", why)       otherwise: the store is not folded, the caller runs conv + depth_to_space.
+    The layer's rows (layer = a ConvLayer; a bare ops.conv has none):
+      ("thin", None)      ops.conv_thin: a 3x3 stride-1 layer, not nearest-x2, <= 4 channels on the launch's OUTPUT side, y.C <= 4, TNR_IMAGE_C4 on, bias / alpha only.
+      ("c4", why)         taps folded into K (TNR_CONV_3x3_C4): the layer owns the C4 packing, x starts a 4-channel buffer, TNR_IMAGE_C4 on.
+      ("im2col", why)     ops.conv_small: the layer owns the column packing, TNR_SMALL_GEMM on, <= 4096 output pixels, a multiple of 8, x.C % 4 == 0, no r1 / r2 / mask / reflect.
+    The launch's rows (tnr_conv_forward):
+      ("tile", "splitk")  conv_tile over a split-K workspace, which excludes every weight stream: <= 16384 output pixels, KinP >= 512, tnr_conv_workspace_bytes > 0.
+                          Always this word: _conv_launch asks the library when it reads it.
+      ("c4", why)         mode is TNR_CONV_3x3_C4 / TNR_CONV_7x7_C4 (what the layer's row above, or a 7x7 image layer, launches).
+      ("wino", None)      Winograd F(2x2, 3x3): TNR_CONV_3x3; TNR_WINO on, x.C >= WINO_MIN_CIN and y.pixels >= WINO_MIN_PIXELS -- or wino=True in their place:
+                          ("wino", "forced") --; bf16x3; y.C % 64 == 0; tnr_conv_wino_bytes > 0.
+      ("stream", why)     pre-split weight stream: TNR_X3_D4 on; TNR_CONV_3x3, or 4x4 stride 2 / its data-gradient with TNR_S2_D4 on; bf16x3 or bf16 operands; y.C % 64 == 0;
+                          tnr_conv_wq_bytes > 0.
+      ("tile", why)       conv_tile: everything else.
+    Everything is read at call time; the keyword arguments ask a what-if instead: mma = the arithmetic, splitk / wino_ok / stream_ok = the library's three late
+    answers, True until asked (_conv_launch asks and, on a decline, asks the plan again with that answer).
+    Below, every row reads: the first condition that holds names why the row is passed over; none holds: the row is taken."""
+    mma = MMA if mma is _LIVE else mma
+    epi = epi or {}
+    if shuffle:
+        no = ((not (SHUFFLE_FOLD and X3_D4 and x.buf.is_cuda) and "switch")
+              or (mma not in _STREAM_MMA and "arithmetic")
+              or (layer is not None and (layer.k != 3 or layer.stride != 1 or layer.ups or layer.cout != 4 * y.C) and "shape")
+              or ((wp.KoutP != 4 * y.C or y.H != 2 * x.H or y.W != 2 * x.W) and "shape")
+              or (not stream_ok and "declined"))
+        return ("tile", no) if no else ("stream", None)
+    why = None          # of the first row passed over
+    if layer is not None:
+        if layer.k == 3 and layer.stride == 1 and not layer.ups and (layer.cin if layer.dgrad else layer.cout) <= 4 and y.C <= 4:
+            why = ((not IMAGE_C4 and "switch")
+                   or ((any(epi.get(n) is not None for n in _FUSED) or epi.get("act", ACT_NONE) != ACT_NONE) and "epilogue"))
+            if not why:
+                return "thin", None
+        if layer.c4 is not None and x.ctot == 4 and x.coff == 0:
+            if IMAGE_C4:
+                return "c4", why
+            why = why or "switch"
+        if layer.col is not None:
+            no = ((not SMALL_GEMM and "switch")
+                  or ((y.pixels > 4096 or y.pixels % 8 or x.C % 4) and "shape")
+                  or ((any(epi.get(n) is not None for n in _FUSED) or epi.get("reflect")) and "epilogue"))
+            if not no:
+                return "im2col", why
+            why = why or no
+    if splitk and wp.KinP >= 512 and y.pixels <= 16384:
+        return "tile", "splitk"
+    if mode in (CONV_3x3_C4, CONV_7x7_C4):
+        return "c4", why
+    if mode == CONV_3x3:
+        no = ((wino is False and "forbidden")
+              or (wino is None and not WINO and "switch")
+              or (wino is None and (x.C < WINO_MIN_CIN or y.pixels < WINO_MIN_PIXELS) and "shape")
+              or (mma != hip.MMA_BF16X3 and "arithmetic")
+              or (y.C % 64 and "shape")
+              or (not wino_ok and "declined"))
+        if not no:
+            return "wino", why or ("forced" if wino else None)
+        why = why or no
+    if mode in (CONV_3x3, CONV_4x4_S2, DGRAD_4x4_S2):
+        no = ((not (X3_D4 and (S2_D4 or mode == CONV_3x3)) and "switch")
+              or (mma not in _STREAM_MMA and "arithmetic")
+              or (y.C % 64 and "shape")
+              or (not stream_ok and "declined"))
+        if not no:
+            return "stream", why
+        why = why or no
+    return "tile", why
+
+
+def _conv_launch(x, wp, y, mode, wino, shuffle, epi, layer=None):
+    """The one tnr_conv_forward path (conv, conv_shuffle2) -> the form launched; None: shuffle cannot be folded and nothing ran.  Descriptor; the
+    library's late answers, each asked where conv_plan's answer hangs on it and fed back into the plan on a decline; the launch; the PROFILE record."""
+    d, said = None, {}
+    while True:
+        form, why = conv_plan(x, wp, y, mode, epi, shuffle, layer, wino, **said)
+        if shuffle and form != "stream":
+            return None
+        if d is None:
+            lib, d = hip.load(), ConvDesc()
+            _conv_desc(d, x, wp, y, mode, **epi)
+            if shuffle:
+                d.Ho, d.Wo, d.Cout, d.shuffle, d.m_hi = x.H, x.W, 4 * y.C, shuffle, 0
+        if why == "splitk":
+            need = lib.tnr_conv_workspace_bytes(C.byref(d))
+            if need > 0:
+                ws = WS.get("splitk@%x" % hip.stream(), need, x.buf.device)
+                d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 8
+                break
+            said["splitk"] = False
+        elif form == "wino":
+            img = _wino_image(lib, d, wp, x.buf.device)
+            if img is not None:
+                d.wq, d.wq_bytes, d.wq_form = img.data_ptr(), img.numel() * 4, 1
+                break
+            assert wino is not True, "this launch cannot run in the Winograd form"
+            said["wino_ok"] = False
+        elif form == "stream":
+            img = _wq_image(lib, d, wp, x.buf.device, tag="shuffle2" if shuffle else None)
+            if img is not None:
+                d.wq, d.wq_bytes = img.data_ptr(), img.numel() * 4
+                break
+            said["stream_ok"] = False
+        else:
+            break
     t0 = PROFILE.begin() if PROFILE is not None else None
-    hip.check(lib.tnr_conv_forward(C.byref(d), hip.stream()), "conv_forward (pixel-shuffle store)")
+    hip.check(lib.tnr_conv_forward(C.byref(d), hip.stream()), "conv_forward")
     if PROFILE is not None:
-        PROFILE.end("conv_tile_3x3", 2.0 * x.pixels * 9 * x.C * 4 * y.C, t0, (x.C, 4 * y.C, x.H, wp.kind))
-    return True
+        fam, taps = _CONV_FAMILY[mode]          # (the Winograd form: the algorithmic FLOP of the convolution it computes)
+        PROFILE.end("conv_wino_3x3" if form == "wino" else fam, 2.0 * d.N * d.Ho * d.Wo * taps * min(x.C, wp.KinP) * d.Cout, t0, (x.C, d.Cout, d.Ho, wp.kind))
+    return form
+
+
+def conv_shuffle2(x, wp, y, layer=None, **epi):
+    """conv (nf -> 4 nf, 3x3) + nn.PixelShuffle(2) + the epilogue's activation in ONE launch (block.pixelshuffle_block, block.py:374-387):
+    y is the SHUFFLED tensor [N, 2 H, 2 W, nf]; the [N, H, W, 4 nf] intermediate and the depth-to-space pass do not exist (tnr_conv_desc.shuffle).
+    Returns False, and launches nothing, unless conv_plan with shuffle=2 says "stream": the caller then runs conv + depth_to_space."""
+    return _conv_launch(x, wp, y, CONV_3x3, None, 2, epi, layer) is not None
 
 
 def conv(x, wp, y, mode=CONV_3x3, wino=None, **epi):
-    """wino: None = the process policy (WINO and the layer's size), True / False = force / forbid the Winograd form for this launch."""
-    d = ConvDesc()
-    _conv_desc(d, x, wp, y, mode, **epi)
-    if y.pixels <= 16384 and wp.KinP >= 512:      # candidates for split-K (tnr_conv_workspace_bytes decides)
-        need = hip.load().tnr_conv_workspace_bytes(C.byref(d))
-        if need > 0:
-            ws = WS.get("splitk@%x" % hip.stream(), need, x.buf.device)
-            d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 8
-    use_wino = (WINO and x.C >= WINO_MIN_CIN and y.pixels >= WINO_MIN_PIXELS) if wino is None else wino
-    if use_wino and mode == CONV_3x3 and d.mma == hip.MMA_BF16X3 and not d.ws and y.C % 64 == 0:
-        img = _wino_image(hip.load(), d, wp, x.buf.device)
-        if img is not None:
-            d.wq, d.wq_bytes, d.wq_form = img.data_ptr(), img.numel() * 4, 1
-        else:
-            assert wino is not True, "this launch cannot run in the Winograd form"
-    if not d.wq and X3_D4 and (mode == CONV_3x3 or (S2_D4 and mode in (CONV_4x4_S2, DGRAD_4x4_S2))) and d.mma in (hip.MMA_BF16X3, hip.MMA_BF16) \
-            and not d.ws and y.C % 64 == 0:
-        img = _wq_image(hip.load(), d, wp, x.buf.device)
-        if img is not None:
-            d.wq, d.wq_bytes = img.data_ptr(), img.numel() * 4
-    if PROFILE is None:
-        hip.check(hip.load().tnr_conv_forward(C.byref(d), hip.stream()), "conv_forward")
-        return
-    t0 = PROFILE.begin()
-    hip.check(hip.load().tnr_conv_forward(C.byref(d), hip.stream()), "conv_forward")
-    taps = {CONV_3x3: 9, CONV_3x3_UP2: 9, CONV_1x1: 1, CONV_3x3_C4: 9, CONV_7x7_C4: 49}.get(mode, 16)
-    opix = y.pixels if mode != DGRAD_4x4_S2 else y.pixels // 4     # each input-grad pixel sees 4 of the 16 taps
-    fam = {CONV_3x3: "conv_tile_3x3", CONV_3x3_UP2: "conv_tile_3x3_up2", CONV_4x4_S2: "conv_tile_4x4s2",
-           DGRAD_4x4_S2: "conv_tile_dgrad4x4s2", CONV_1x1: "conv_tile_1x1", CONV_3x3_C4: "conv_tile_3x3_c4", CONV_7x7_C4: "conv_tile_7x7_c4"}[mode]
-    if d.wq_form == 1:
-        fam = "conv_wino_3x3"          # (algorithmic FLOP of the convolution it computes: 9 taps)
-    PROFILE.end(fam, 2.0 * opix * taps * min(x.C, wp.KinP) * y.C, t0, (x.C, y.C, y.H, wp.kind))
+    """One tnr_conv_forward launch in the form conv_plan names.  wino: None = the process policy (WINO and the layer's size), True / False =
+    force / forbid the Winograd form for this launch."""
+    _conv_launch(x, wp, y, mode, wino, 0, epi)
 
 
 CHAIN_MAX = 6
@@ -477,7 +555,6 @@ _SWEEP_FORM_DMA = os.environ.get("TNR_SWEEP_FORM", "")[:2] == "dm"      # (the f
 COLLECTIVES_IN_FLIGHT = False   # True (dp.py) from the first gradient bucket handed to RCCL on the side stream until the compute stream has waited for all
 COUNTERS = {"one_launch_next_to_collectives": 0, "per_layer_next_to_collectives": 0}      # dense blocks launched while gradient buckets were in flight
 _cu_counts = {}
-_LIVE = object()                # dense_block_plan: "read the module's state now" (the default of every what-if argument)
 
 
 def _cus(dev):
@@ -830,14 +907,6 @@ def wgrad_thin7(big, small4, dw, db, flip, rpad=0, off=0, alpha=1.0, beta=1.0):
                                   dw.data_ptr(), hip.ptr(db), alpha, beta, ws.data_ptr(), ws.numel() * 8, hip.stream()), "wgrad_thin7")
     if PROFILE is not None:
         PROFILE.end("wgrad_thin", 2.0 * big.N * (big.H + 2 * rpad) * (big.W + 2 * rpad) * 49 * big.C * cs, t0, (big.C, cs, big.H, 70 + int(flip)))
-
-
-def small_gemm_ok(x, y, k, stride, epi):
-    """A k x k convolution runs as im2col + split-K GEMM when it has <= 4096 output pixels (tiles of the direct
-    kernel would be mostly padding and too few to fill the chip) and a plain epilogue."""
-    if not SMALL_GEMM or y.pixels > 4096 or (y.pixels % 8) != 0 or (x.C % 4) != 0:
-        return False
-    return not any(epi.get(n) is not None for n in ("r1", "r2", "mask")) and not epi.get("reflect")
 
 
 def conv_small(x, wp_col, y, k, stride, pad=1, **epi):
