@@ -601,6 +601,36 @@ int tnr_gram_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, int32_t C, float s
 int tnr_gram_bwd(tnr_view x, const float *S, int32_t N, int32_t H, int32_t W, int32_t C, float scale, int32_t mma, tnr_view dx,
                  int32_t accumulate, void *stream);
 
+/* --- contextual loss of a pair of activation views (Contextual_Loss 'cosine' / 'regular', modules/loss.py:769-1092;
+ * csrc/contextual.hip) ----------------------------------------------------------------------------------------------------------
+ * x / y: NHWC views [N, H, W, C], C a multiple of 64 up to 512.  P <= 4096 positions per image: all H W of them (idx NULL) or the
+ * device list idx[P] of a random pooling (the same for every image).  The matrix D is fp32 [N][P][LD], LD = P rounded up to 4
+ * (tnr_cx_matrix_bytes), and is transformed in place: tnr_cx_distance writes d, tnr_cx_rows turns it into cx (negated where d == 0)
+ * and tnr_cx_grad_rows into d loss / d cos.  mma: TNR_MMA_F32 or TNR_MMA_BF16X3.  No floating-point atomics anywhere: two runs are
+ * bit-identical; ties of the row minimum / column maximum go to the smaller index.
+ * tnr_cx_sums:      sums[c] = sum of y over batch and positions (c < C), sums[C] = N P (the caller may all-reduce the C + 1 floats).
+ * tnr_cx_prepare:   xh[n][p][:] = (x - sums / count) / max(||.||, 1e-12), nrm[n][p] = that clamped norm.
+ * tnr_cx_distance:  d[n][i][j] = max((1 - <xh[n][i], yh[n][j]>) / 2, 0).
+ * tnr_cx_rows:      rowmin / argmin [N][P], rowE[n][i] = sum_j cx_ij d_ij, colpack [N][P] 64-bit words (value bits, ~row).
+ * tnr_cx_finalize:  colmax / argmax [N][P], CS[n] = mean_j colmax, gcoef[n] = -1 / (N P CS[n]), loss[0] = mean_n -log CS[n].
+ * tnr_cx_grad_rows: D <- d loss / d cos (dwin: [N][P] floats of scratch).   tnr_cx_grad_gemm: dxh[n][i][:] = sum_k D[n][i][k] yh[n][k][:].
+ * tnr_cx_norm_bwd:  the normalisation's backward, scattered into the view dx over ALL H W positions: inv[s] = the slot of position s
+ *   in the pooling list or -1 (such positions get zeros); inv NULL = no pooling. */
+int64_t tnr_cx_sums_workspace_bytes(int32_t N, int32_t P, int32_t C);
+int tnr_cx_sums(tnr_view y, int32_t N, int32_t H, int32_t W, int32_t C, const int32_t *idx, int32_t P, float *sums, void *ws, int64_t ws_bytes,
+                void *stream);
+int tnr_cx_prepare(tnr_view x, int32_t N, int32_t H, int32_t W, int32_t C, const int32_t *idx, int32_t P, const float *sums, float *xh, float *nrm,
+                   void *stream);
+int64_t tnr_cx_matrix_bytes(int32_t N, int32_t P);
+int tnr_cx_distance(const float *xh, const float *yh, int32_t N, int32_t P, int32_t C, int32_t mma, float *D, void *stream);
+int tnr_cx_rows(float *D, int32_t N, int32_t P, float b, float h, float *rowmin, int32_t *argmin, float *rowE, void *colpack, void *stream);
+int tnr_cx_finalize(const void *colpack, int32_t N, int32_t P, float *colmax, int32_t *argmax, float *CS, float *gcoef, float *loss, void *stream);
+int tnr_cx_grad_rows(float *D, const float *xh, const float *yh, int32_t N, int32_t P, int32_t C, float h, const float *rowmin,
+                     const int32_t *argmin, const float *rowE, const int32_t *argmax, const float *gcoef, float *dwin, void *stream);
+int tnr_cx_grad_gemm(const float *G, const float *yh, int32_t N, int32_t P, int32_t C, int32_t mma, float *dxh, void *stream);
+int tnr_cx_norm_bwd(const float *dxh, const float *xh, const float *nrm, int32_t N, int32_t H, int32_t W, int32_t C, int32_t P, const int32_t *inv,
+                    tnr_view dx, void *stream);
+
 /* --- optimiser (torch.optim.Adam optimizers.py:130-132; clip_grad_norm_ base_model.py:911-922) -- */
 int tnr_sumsq(const float *g, int64_t n, double *out, void *ws, void *stream);
 int tnr_clip_by_norm(float *g, int64_t n, const double *sumsq, float max_norm, void *stream);

@@ -190,6 +190,16 @@ _SIGS = {
     "tnr_gram_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i]),
     "tnr_gram_fwd": (c_i, [CView, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p]),
     "tnr_gram_bwd": (c_i, [CView, c_p, c_i, c_i, c_i, c_i, c_f, c_i, CView, c_i, c_p]),
+    "tnr_cx_sums_workspace_bytes": (c_l, [c_i, c_i, c_i]),
+    "tnr_cx_sums": (c_i, [CView, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_l, c_p]),
+    "tnr_cx_prepare": (c_i, [CView, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
+    "tnr_cx_matrix_bytes": (c_l, [c_i, c_i]),
+    "tnr_cx_distance": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "tnr_cx_rows": (c_i, [c_p, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p]),
+    "tnr_cx_finalize": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "tnr_cx_grad_rows": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "tnr_cx_grad_gemm": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "tnr_cx_norm_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, CView, c_p]),
     "tnr_sumsq": (c_i, [c_p, c_l, c_p, c_p, c_p]),
     "tnr_clip_by_norm": (c_i, [c_p, c_l, c_p, c_f, c_p]),
     "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),

@@ -206,6 +206,14 @@ def get_loss_fn(loss_type=None, weight=0, recurrent=False, reduction="mean", net
         fea_loss_f = get_loss_fn(parts[2], recurrent=True, reduction="mean", device=device)
         network = networks.define_F(opt).to(device)
         loss_function = PerceptualLoss(criterion=fea_loss_f, network=network, opt=opt)
+    elif loss_type == "contextual":
+        # losses.py:129-135; the feature network's weights resolve as networks.define_F's do
+        from .modules.contextual import Contextual_Loss
+        layers = opt["train"].get("cx_vgg_layers", {"conv3_2": 1.0, "conv4_2": 1.0})
+        z_norm = opt["datasets"]["train"].get("znorm", False)
+        loss_function = Contextual_Loss(layers, max_1d_size=64, distance_type="cosine", calc_type="regular", z_norm=z_norm,
+                                        load_path=(opt["train"].get("perceptual_opt") or {}).get("pretrained_path", None),
+                                        allow_random_init=bool(opt["train"].get("perceptual_allow_random_init")))
     elif loss_type in ("ssim", "SSIM", "ms-ssim", "MSSSIM"):
         # losses.py:70-85; `opt` is the train block here (losses.py:799-801)
         image_channels = ((opt or {}).get("image_channels") or 3) if allow_featnets else 1
@@ -383,11 +391,11 @@ def ops_mean(pred):
 
 
 class GeneratorLoss(nn.Module):
-    """Weighted list of generator losses (losses.py:607-962): pixel, hfen, tv, feature, then the precise list grad, ssim; same
-    order and names."""
+    """Weighted list of generator losses (losses.py:607-962): pixel, hfen, tv, contextual, feature, then the precise list grad, ssim;
+    same order and names."""
 
     _UNSUPPORTED = ("color_weight", "avg_weight", "ms_weight", "spl_weight", "of_weight",
-                    "lpips_weight", "cx_weight", "fft_weight",
+                    "lpips_weight", "fft_weight",
                     "fdpl_weight", "range_weight")
 
     def __init__(self, opt=None, device="cpu", allow_featnets=True):
@@ -409,6 +417,10 @@ class GeneratorLoss(nn.Module):
         tv_type = check_loss_names(tv_type=train_opt.get("tv_type"), tv_norm=train_opt.get("tv_norm"))
         if tv_weight > 0 and tv_type:
             self.loss_list.append(get_loss_fn(tv_type, tv_weight, device=device))
+        cx_weight = (train_opt.get("cx_weight", 0) or 0) if allow_featnets else 0          # losses.py:686-694,730-733
+        cx_type = train_opt.get("cx_type", None) if allow_featnets else None
+        if cx_weight > 0 and cx_type:
+            self.loss_list.append(get_loss_fn(cx_type, cx_weight, device=device, opt=opt))
         feature_weight = (train_opt.get("feature_weight", 0) or 0) if allow_featnets else 0
         style_weight = (train_opt.get("style_weight", 0) or 0) if allow_featnets else 0
         feat_opts = train_opt.get("perceptual_opt")
@@ -446,6 +458,12 @@ class GeneratorLoss(nn.Module):
         if self.dp_group is not None and getattr(l["function"], "sum_reduced", False):
             effective = effective * float(self.dp_group.world_size)
         return effective
+
+    def _contextual(self, f, sr, hr):
+        """The contextual term on the plain (sr, hr) pair.  Under data parallelism the channel mean of the HR taps is all-reduced inside
+        (the reference forms it over the gathered batch); the loss is a batch mean over equal shards like every other term."""
+        f.dp_group = self.dp_group
+        return f(sr, hr)
 
     @staticmethod
     def _fea_effective(l, percep_loss, style_loss):
@@ -489,6 +507,8 @@ class GeneratorLoss(nn.Module):
                 effective = l["weight"] * (1 - f(lp("sr", sr), lp("hr", hr)))
             elif "fea-vgg" in name:
                 effective = self._fea_effective(l, *f(sr, hr))                      # unfiltered
+            elif name == "contextual":
+                effective = l["weight"] * self._contextual(f, sr, hr)               # unfiltered: the last branch of calc_losses_fs
             else:
                 # everything else sees the unfiltered pair.  That includes grad-2d-* / grad-4d-*: the reference's low-pass branch asks
                 # for 'gradient' in the name (losses.py:879), which these names do not contain -- its quirk, kept
@@ -534,6 +554,8 @@ class GeneratorLoss(nn.Module):
                 effective = self._fea_effective(l, *l["function"](sr, hr))
             elif "tv" in l["name"]:
                 effective = self._effective(l, l["function"](self._fp32(sr)))              # fake_H alone
+            elif l["name"] == "contextual":
+                effective = l["weight"] * self._contextual(l["function"], sr, hr)
             elif isinstance(l["function"], (IL.HFENLoss, IL._Criterion)):
                 effective = self._effective(l, l["function"](self._fp32(sr), self._fp32(hr)))   # fp32 kernels with or without AMP
             else:

@@ -1368,6 +1368,81 @@ def gram_bwd(x, S, scale, dx, accumulate=False):
               "gram_bwd")
 
 
+# Contextual loss of two activation views and its gradient (csrc/contextual.hip).  Like the Gram matrix: on the fp32 activations and in
+# the arithmetic of TNR_MMA, also under `use_amp`.
+def _cx_ws(name, nbytes, dev, dtype=torch.float32):
+    return WS.get("cx_%s@%x" % (name, hip.stream()), nbytes, dev).view(dtype)
+
+
+def cx_sums(y, idx, P, sums):
+    """sums[c] = sum of y over batch and (pooled) positions, sums[C] = the count: C + 1 floats a data-parallel group may all-reduce."""
+    lib, dev = hip.load(), y.buf.device
+    nbytes = lib.tnr_cx_sums_workspace_bytes(y.N, P, y.C)
+    ws = WS.get("cx_sums@%x" % hip.stream(), nbytes, dev)
+    hip.check(lib.tnr_cx_sums(y.c(), y.N, y.H, y.W, y.C, hip.ptr(idx), P, sums.data_ptr(), ws.data_ptr(), ws.numel() * 8, hip.stream()), "cx_sums")
+
+
+def cx_prepare(x, idx, P, sums, xh, nrm):
+    hip.check(hip.load().tnr_cx_prepare(x.c(), x.N, x.H, x.W, x.C, hip.ptr(idx), P, sums.data_ptr(), xh.data_ptr(), nrm.data_ptr(), hip.stream()),
+              "cx_prepare")
+
+
+def cx_layer(x, y, idx_x=None, idx_y=None, inv_x=None, b=1.0, h=0.5, dx=None, group=None, probe=None):
+    """The contextual loss of the views x (SR tap) and y (HR tap): -> {'loss' (0-d), 'CS', 'rowmin', 'argmin', 'colmax', 'argmax'}.
+    idx_x / idx_y: int32 device lists of the P pooled positions of each operand (None: all H W), inv_x: int32 [H W] map position -> slot
+    or -1 (needed with idx_x when `dx` is given).  With the view `dx` the gradient kernels run too and d loss / d x is written into it
+    (zeros at unsampled positions); without it they do not run.  `probe`, a dict, receives a copy of the distance matrix [N, P, P]
+    (tests).  `group`: the data-parallel group whose ranks share the channel mean."""
+    lib, dev, st = hip.load(), x.buf.device, hip.stream()
+    N, C = x.N, x.C
+    P = x.H * x.W if idx_x is None else idx_x.numel()
+    Py = y.H * y.W if idx_y is None else idx_y.numel()
+    if y.N != N or y.C != C or Py != P:
+        raise ValueError("cx_layer: operands of %d x %d x %d and %d x %d x %d (images x positions x channels)" % (N, P, C, y.N, Py, y.C))
+    for t in (idx_x, idx_y, inv_x):
+        assert t is None or (t.dtype == torch.int32 and t.is_cuda and t.is_contiguous())
+    sums = torch.empty(C + 1, dtype=torch.float32, device=dev)
+    cx_sums(y, idx_y, P, sums)
+    if group is not None:
+        group.all_reduce_sum(sums)
+    feat = _cx_ws("feat", 3 * N * P * C * 4, dev)
+    xh, yh, dxh = feat[:N * P * C], feat[N * P * C:2 * N * P * C], feat[2 * N * P * C:3 * N * P * C]
+    nrm_x = torch.empty(N * P, dtype=torch.float32, device=dev)
+    nrm_y = torch.empty(N * P, dtype=torch.float32, device=dev)
+    cx_prepare(x, idx_x, P, sums, xh, nrm_x)
+    cx_prepare(y, idx_y, P, sums, yh, nrm_y)
+    D = _cx_ws("matrix", lib.tnr_cx_matrix_bytes(N, P), dev)
+    hip.check(lib.tnr_cx_distance(xh.data_ptr(), yh.data_ptr(), N, P, C, FP32_MMA, D.data_ptr(), st), "cx_distance")
+    if probe is not None:
+        ld = (P + 3) // 4 * 4
+        probe["d"] = D[:N * P * ld].view(N, P, ld)[:, :, :P].clone()
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = {"rowmin": torch.empty((N, P), **f32), "argmin": torch.empty((N, P), **i32), "colmax": torch.empty((N, P), **f32),
+           "argmax": torch.empty((N, P), **i32), "CS": torch.empty(N, **f32), "loss": torch.empty((), **f32)}
+    rowE, gcoef = torch.empty((N, P), **f32), torch.empty(N, **f32)
+    colpack = torch.empty((N, P), dtype=torch.int64, device=dev)
+    hip.check(lib.tnr_cx_rows(D.data_ptr(), N, P, float(b), float(h), out["rowmin"].data_ptr(), out["argmin"].data_ptr(), rowE.data_ptr(),
+                              colpack.data_ptr(), st), "cx_rows")
+    hip.check(lib.tnr_cx_finalize(colpack.data_ptr(), N, P, out["colmax"].data_ptr(), out["argmax"].data_ptr(), out["CS"].data_ptr(),
+                                  gcoef.data_ptr(), out["loss"].data_ptr(), st), "cx_finalize")
+    if dx is not None:
+        if idx_x is not None and inv_x is None:
+            raise ValueError("cx_layer: a pooled gradient needs the inverse index map")
+        cx_grad(D, xh, yh, dxh, nrm_x, N, P, C, h, out, rowE, gcoef, inv_x, dx)
+    return out
+
+
+def cx_grad(D, xh, yh, dxh, nrm_x, N, P, C, h, out, rowE, gcoef, inv_x, dx):
+    """The three gradient launches of cx_layer (a function of its own so that a test can see whether they ran)."""
+    lib, st = hip.load(), hip.stream()
+    dwin = torch.empty((N, P), dtype=torch.float32, device=D.device)
+    hip.check(lib.tnr_cx_grad_rows(D.data_ptr(), xh.data_ptr(), yh.data_ptr(), N, P, C, float(h), out["rowmin"].data_ptr(), out["argmin"].data_ptr(),
+                                   rowE.data_ptr(), out["argmax"].data_ptr(), gcoef.data_ptr(), dwin.data_ptr(), st), "cx_grad_rows")
+    hip.check(lib.tnr_cx_grad_gemm(D.data_ptr(), yh.data_ptr(), N, P, C, FP32_MMA, dxh.data_ptr(), st), "cx_grad_gemm")
+    hip.check(lib.tnr_cx_norm_bwd(dxh.data_ptr(), xh.data_ptr(), nrm_x.data_ptr(), N, dx.H, dx.W, C, P, hip.ptr(inv_x), dx.c(), st), "cx_norm_bwd")
+
+
 def ragan_phase_a(pf, pr, sums):
     hip.check(hip.load().tnr_ragan_phase_a(pf.data_ptr(), pr.data_ptr(), pf.numel(), sums.data_ptr(), _reduce_ws(pf.device).data_ptr(), hip.stream()), "ragan_a")
 
