@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 #include "../../include/trainner_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -25,6 +26,33 @@ unsigned *tnr_fault_word_or(unsigned *fallback);      // the registered fault la
             return TNR_EINVAL;            \
         }                                 \
     } while (0)
+
+// One kernel and the dynamic LDS its launches ask for (tnr_kernel_setup).
+struct tnr_kernel_lds {
+    const void *fn;
+    size_t lds;
+    template <class F> tnr_kernel_lds(F *f, size_t bytes) : fn(reinterpret_cast<const void *>(f)), lds(bytes) {}
+};
+
+// The once-per-process setup of a launch site: raises the dynamic-LDS limit of every listed kernel and leaves the device's CU count
+// in *cus.  `cus` points at the call site's own `static int cus = 0`: while it is positive the call does nothing and returns TNR_OK.
+// On failure *cus stays 0, so the NEXT call of the site tries again (nothing is latched), the error text names `who`, and the result
+// is TNR_ELAUNCH.
+inline int tnr_kernel_setup(int *cus, const char *who, std::initializer_list<tnr_kernel_lds> kernels) {
+    if (*cus > 0) return TNR_OK;
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) {
+        tnr_set_error("%s: cannot query the device", who);
+        return TNR_ELAUNCH;
+    }
+    for (const tnr_kernel_lds &k : kernels)
+        if (hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) != hipSuccess) {
+            tnr_set_error("%s: cannot raise dynamic LDS to %zu bytes", who, k.lds);
+            return TNR_ELAUNCH;
+        }
+    *cus = n;
+    return TNR_OK;
+}
 
 static inline int tnr_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t tnr_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

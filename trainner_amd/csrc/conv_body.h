@@ -138,6 +138,53 @@ struct ConvK {
     int noise_pos; float noise_sigma; unsigned noise_k0, noise_k1, noise_pix0;
 };
 
+// Every ConvK member that follows from the descriptor alone; a new member is filled HERE and nowhere else.  What a launcher adds is
+// its own tile grid (tiles_x, tiles_y, ncb) and, in tnr_conv_forward, the split-K rewrite.  The noise fields are copied whatever
+// noise_pos says: the kernels read them only when noise_pos != 0, so a launcher that demands noise_pos == 0 needs no special case.
+inline ConvK conv_k_from_desc(const tnr_conv_desc &d) {
+    ConvK k{};      // (value-initialised: a member this function forgets is zero, not garbage)
+    k.x = d.x.ptr; k.x_ct = d.x.ctot; k.x_co = d.x.coff;
+    k.N = d.N; k.H = d.H; k.W = d.W; k.Cin = d.Cin;
+    k.wp = d.wp; k.KinP = d.KinP; k.KoutP = d.KoutP;
+    k.y = d.y.ptr; k.y_ct = d.y.ctot; k.y_co = d.y.coff; k.Ho = d.Ho; k.Wo = d.Wo; k.Cout = d.Cout;
+    k.bias = d.bias; k.act = d.act; k.slope = d.slope; k.alpha = d.alpha;
+    k.r1 = d.r1.ptr; k.r1_ct = d.r1.ctot; k.r1_co = d.r1.coff; k.r1_ch = d.r1_ch; k.beta1 = d.beta1;
+    k.r2 = d.r2.ptr; k.r2_ct = d.r2.ctot; k.r2_co = d.r2.coff; k.alpha2 = d.alpha2;
+    k.m = d.m.ptr; k.m_ct = d.m.ctot; k.m_co = d.m.coff; k.m_lo = d.m_lo; k.m_hi = d.m_hi; k.m_slope = d.m_slope;
+    k.noise_pos = d.noise_pos; k.noise_sigma = d.noise_sigma; k.noise_k0 = d.noise_key0; k.noise_k1 = d.noise_key1; k.noise_pix0 = d.noise_pix0;
+    const bool dg = d.mode == TNR_DGRAD_4x4_S2;      // the strided data-gradient tiles its INPUT (gout) grid
+    k.th_space = dg ? d.H : d.Ho; k.tw_space = dg ? d.W : d.Wo;
+    k.ksplit = 1; k.split_stride = 0; k.bf = d.mma; k.reflect = d.pad_mode == 1;
+    return k;
+}
+
+// The arguments the weight-stream kernels share (D4K, S2K, WinoK: a ConvK, the stream, a tw x th tile grid over 64-cout blocks;
+// `par`: 4 parity classes for the strided data-gradient, else 1).  false: the grid does not fit 31 bits.
+template <class StreamK>
+bool stream_k_from_desc(StreamK &c, const tnr_conv_desc &d, int64_t wq_bytes, int tw, int th, int par) {
+    c.a = conv_k_from_desc(d);
+    c.wq = static_cast<const float *>(d.wq);
+    c.wq_bytes = (int)wq_bytes;
+    c.nck = d.Cin / 16;
+    c.a.tiles_x = c.tiles_x = tnr_cdiv(c.a.tw_space, tw);
+    c.a.tiles_y = c.tiles_y = tnr_cdiv(c.a.th_space, th);
+    c.a.ncb = c.ncb = d.Cout / 64;
+    const int64_t tiles = (int64_t)c.tiles_x * c.tiles_y * c.ncb * d.N * par;
+    c.tiles = (int)tiles;
+    return tiles < (1LL << 31);
+}
+
+// x, y and the optional r1 / r2 / mask views (with r1_ch and the mask's channel range) start and stride on 4-channel boundaries
+inline bool view_aligned(const tnr_view &v) { return (v.ctot % 4) == 0 && (v.coff % 4) == 0; }
+inline bool views_aligned(const tnr_conv_desc &d) {
+    return view_aligned(d.x) && view_aligned(d.y) && (d.r1.ptr == nullptr || (view_aligned(d.r1) && (d.r1_ch % 4) == 0)) &&
+           (d.r2.ptr == nullptr || view_aligned(d.r2)) && (d.m.ptr == nullptr || (view_aligned(d.m) && (d.m_lo % 4) == 0 && (d.m_hi % 4) == 0));
+}
+// input and output buffers stay below 2^30 elements = 4 GiB, the range of a buffer descriptor's 32-bit byte offset
+inline bool buffers_addressable(const tnr_conv_desc &d) {
+    return (int64_t)d.N * d.H * d.W * d.x.ctot < (1LL << 30) && (int64_t)d.N * d.Ho * d.Wo * d.y.ctot < (1LL << 30);
+}
+
 #ifdef TNR_TIMELINE   /* tools/probes/conv_timeline.hip: per-workgroup s_memtime stamps, 8 per body call */
 __device__ unsigned long long tnr_timeline[8192 * 8 * 8];
 __device__ int tnr_timeline_call[8192];      /* which body call of the workgroup is running (chain kernel: stage pass) */

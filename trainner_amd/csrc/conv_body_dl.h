@@ -366,15 +366,9 @@ template <int NT, int MT>
 int launch_conv3x3_dk8(const ConvK &k, int64_t tiles, hipStream_t s) {
     using G = Dk8Geom<NT, MT>;
     static_assert(G::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-    static bool attr_done = false;
     auto fn = conv3x3_dk8_kernel<NT, MT>;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES) != hipSuccess) {
-            tnr_set_error("conv3x3_dk8: cannot raise dynamic LDS to %zu bytes", G::LDS_BYTES);
-            return TNR_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    static int cus = 0;
+    if (const int rc = tnr_kernel_setup(&cus, "conv3x3_dk8", {{fn, G::LDS_BYTES}})) return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)tiles), dim3(256), G::LDS_BYTES, s, k);
     return tnr_check_launch("conv3x3_dk8");
 }
@@ -406,15 +400,9 @@ int launch_conv3x3_dl(ConvK k, hipStream_t s) {
     k.tiles_y = tnr_cdiv(k.th_space, G::TH);
     k.ncb = tnr_cdiv(k.Cout, G::NC);
     const int64_t tiles = (int64_t)k.tiles_x * k.tiles_y * k.ncb * k.N;
-    static bool attr_done = false;
     auto fn = conv3x3_dl_kernel<2, NL>;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES) != hipSuccess) {
-            tnr_set_error("conv3x3_dl: cannot raise dynamic LDS to %zu bytes", G::LDS_BYTES);
-            return TNR_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    static int cus = 0;
+    if (const int rc = tnr_kernel_setup(&cus, "conv3x3_dl", {{fn, G::LDS_BYTES}})) return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)tiles), dim3(512 + 64 * NL), G::LDS_BYTES, s, k);
     return tnr_check_launch("conv3x3_dl");
 }

@@ -315,22 +315,15 @@ static_assert(chain_lds(2) <= 80 * 1024, "two chain workgroups per CU");
 int chain_capacity(int *out) {
     static int cap = 0;
     if (cap == 0) {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-            tnr_set_error("conv_chain: cannot query the device");
-            return TNR_ELAUNCH;
-        }
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv_chain_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)chain_lds()) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_chain_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)chain_lds()) != hipSuccess ||
+        static int cus = 0;
+        if (const int rc = tnr_kernel_setup(&cus, "conv_chain", {{conv_chain_kernel<0>, chain_lds()}, {conv_chain_kernel<1>, chain_lds()},
 #ifdef TNR_CONV_DL_EXPERIMENT
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_chain_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)chain_lds()) != hipSuccess ||
+                                                                  {conv_chain_kernel<0, 2>, chain_lds()},
 #endif
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_chain_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)chain_lds(2)) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_chain_kernel<0>, 256, chain_lds()) != hipSuccess) {
+                                                                  {conv_chain_kernel<2>, chain_lds(2)}}))
+            return rc;
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_chain_kernel<0>, 256, chain_lds()) != hipSuccess) {
             tnr_set_error("conv_chain: cannot size the grid");
             return TNR_ELAUNCH;
         }
@@ -342,7 +335,7 @@ int chain_capacity(int *out) {
             tnr_set_error("conv_chain: the split-operand form does not reach %d workgroups per CU (%d)", per_cu, per_cu_x3);
             return TNR_ELAUNCH;
         }
-        if (per_cu < 1 || cus < 1) {
+        if (per_cu < 1) {
             tnr_set_error("conv_chain: kernel does not fit a CU");
             return TNR_ELAUNCH;
         }
@@ -388,30 +381,13 @@ extern "C" int tnr_conv_chain(const tnr_conv_desc *stages, const int32_t *fresh_
         TNR_REQUIRE(d->KinP >= 2 * TNR_CK, "conv_chain: stage %d needs at least 32 (padded) input channels", i);
         TNR_REQUIRE((d->Cout % 32) == 0 && d->KoutP == d->Cout && (d->Cin % 4) == 0 && (d->KinP % TNR_CK) == 0 && d->Cin <= d->KinP,
                     "conv_chain: stage %d: Cout must be a multiple of 32, Cin of 4", i);
-        TNR_REQUIRE((d->x.ctot % 4) == 0 && (d->x.coff % 4) == 0 && (d->y.ctot % 4) == 0 && (d->y.coff % 4) == 0,
-                    "conv_chain: stage %d: views must be 4-channel aligned", i);
-        TNR_REQUIRE(d->r1.ptr == nullptr || ((d->r1.ctot % 4) == 0 && (d->r1.coff % 4) == 0 && (d->r1_ch % 4) == 0),
-                    "conv_chain: stage %d: r1 view must be 4-channel aligned", i);
-        TNR_REQUIRE(d->r2.ptr == nullptr || ((d->r2.ctot % 4) == 0 && (d->r2.coff % 4) == 0), "conv_chain: stage %d: r2 view", i);
+        TNR_REQUIRE(views_aligned(*d), "conv_chain: stage %d: x / y / r1 (+ r1_ch) / r2 / mask (+ range) views must be 4-channel aligned", i);
         TNR_REQUIRE(d->noise_pos >= 0 && d->noise_pos <= 2, "conv_chain: stage %d: bad noise_pos %d", i, d->noise_pos);
-        TNR_REQUIRE(d->m.ptr == nullptr || ((d->m.ctot % 4) == 0 && (d->m.coff % 4) == 0 && (d->m_lo % 4) == 0 && (d->m_hi % 4) == 0),
-                    "conv_chain: stage %d: mask view", i);
-        TNR_REQUIRE((int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 30) && (int64_t)d->N * d->H * d->W * d->y.ctot < (1LL << 30),
-                    "conv_chain: stage %d: buffers above 4 GiB are not addressable through a buffer descriptor", i);
+        TNR_REQUIRE(buffers_addressable(*d), "conv_chain: stage %d: buffers above 4 GiB are not addressable through a buffer descriptor", i);
         TNR_REQUIRE(fresh_from[i] < d->Cin && (i > 0 || fresh_from[i] < 0), "conv_chain: stage %d: bad fresh_from %d", i, fresh_from[i]);
         ConvK &k = c.st[i];
-        k.x = d->x.ptr; k.x_ct = d->x.ctot; k.x_co = d->x.coff;
-        k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin;
-        k.wp = d->wp; k.KinP = d->KinP; k.KoutP = d->KoutP;
-        k.y = d->y.ptr; k.y_ct = d->y.ctot; k.y_co = d->y.coff; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-        k.bias = d->bias; k.act = d->act; k.slope = d->slope; k.alpha = d->alpha;
-        k.r1 = d->r1.ptr; k.r1_ct = d->r1.ctot; k.r1_co = d->r1.coff; k.r1_ch = d->r1_ch; k.beta1 = d->beta1;
-        k.r2 = d->r2.ptr; k.r2_ct = d->r2.ctot; k.r2_co = d->r2.coff; k.alpha2 = d->alpha2;
-        k.m = d->m.ptr; k.m_ct = d->m.ctot; k.m_co = d->m.coff; k.m_lo = d->m_lo; k.m_hi = d->m_hi; k.m_slope = d->m_slope;
-        k.noise_pos = d->noise_pos; k.noise_sigma = d->noise_sigma; k.noise_k0 = d->noise_key0; k.noise_k1 = d->noise_key1; k.noise_pix0 = d->noise_pix0;
+        k = conv_k_from_desc(*d);
         k.tiles_x = c.tiles_x; k.tiles_y = c.tiles_y; k.ncb = d->KoutP / 32;
-        k.th_space = d->Ho; k.tw_space = d->Wo;
-        k.ksplit = 1; k.split_stride = 0; k.bf = d->mma; k.reflect = d->pad_mode == 1;
         TNR_REQUIRE(d->mma == d0.mma, "conv_chain: stage %d: all stages share one matrix-core precision", i);
         c.wait_chunk[i] = fresh_from[i] < 0 ? -1 : fresh_from[i] / TNR_CK;
     }
@@ -438,16 +414,7 @@ extern "C" int tnr_conv_chain(const tnr_conv_desc *stages, const int32_t *fresh_
         for (int i = 0; i < n; ++i) ok8 = ok8 && c.st[i].Cin == c.st[i].KinP && !c.st[i].reflect;
         if (ok8) {
             static int cus = 0;
-            if (cus == 0) {
-                int dev = 0;
-                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(conv_chain_x3w8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)CX3::LDS_BYTES) != hipSuccess || cus < 1) {
-                    cus = 0;
-                    tnr_set_error("conv_chain: cannot set up the 8-wave form");
-                    return TNR_ELAUNCH;
-                }
-            }
+            if (const int rc = tnr_kernel_setup(&cus, "conv_chain (8-wave form)", {{conv_chain_x3w8_kernel, CX3::LDS_BYTES}})) return rc;
             ChainK c8 = c;
             c8.tiles_x = tnr_cdiv(d0.Wo, CX3::TW);
             c8.tiles_y = tnr_cdiv(d0.Ho, CX3::TH);

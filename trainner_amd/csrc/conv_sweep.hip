@@ -1497,7 +1497,7 @@ bool s2_ok(const tnr_conv_desc *d) {
     return (d->mma == TNR_MMA_BF16X3 || d->mma == TNR_MMA_BF16) && d->pad_mode == 0 && d->shuffle == 0 && (d->Cout % 64) == 0 && d->KoutP == d->Cout &&
            d->Cin == d->KinP && (d->Cin % 16) == 0 && d->Cin >= 32 && tw >= 32 && th >= 8 &&
            (dg ? (d->Ho == 2 * d->H && d->Wo == 2 * d->W) : (d->H == 2 * d->Ho && d->W == 2 * d->Wo)) &&
-           (int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 30) && (int64_t)d->N * d->Ho * d->Wo * d->y.ctot < (1LL << 30) &&
+           buffers_addressable(*d) &&
            (int64_t)(d->Cout / 64) * (d->Cin / 16) * 4 * S2_NU * SW_UNIT_FLOATS * (int64_t)sizeof(float) < (1LL << 31);
 }
 
@@ -1509,7 +1509,7 @@ bool d4_ok(const tnr_conv_desc *d) {
     return d->mode == TNR_CONV_3x3 && (d->mma == TNR_MMA_BF16X3 || d->mma == TNR_MMA_BF16) && (d->pad_mode == 0 || (d->pad_mode == 1 && d->H >= 2 && d->W >= 2)) &&
            (d->Cout % 64) == 0 && d->KoutP == d->Cout &&
            d->Cin == d->KinP && (d->Cin % 16) == 0 && d->Cin >= 32 && d->Ho == d->H && d->Wo == d->W && d->W >= 32 && d->H >= 8 &&
-           (int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 30) && (int64_t)d->N * d->H * d->W * d->y.ctot < (1LL << 30) &&
+           buffers_addressable(*d) &&
            (int64_t)(d->Cout / 64) * (d->Cin / 16) * 18 * SW_UNIT_FLOATS * (int64_t)sizeof(float) < (1LL << 31);
 }
 
@@ -1531,12 +1531,9 @@ bool sweep_pattern(const tnr_conv_desc *st, int n, const char **why) {
         if (d.Cin != d0.Cin + 32 * i || d.KinP != d.Cin) return no("input channels do not grow by 32 per stage");
         if (d.Cout != (i < 4 ? 32 : 64) || d.KoutP != d.Cout) return no("output channels are not 32, 32, 32, 32, 64");
         if (i < 4 && (d.y.ptr != d0.x.ptr || d.y.ctot != d0.x.ctot || d.y.coff != d0.x.coff + d.Cin)) return no("stage output is not the next channel group");
-        if ((d.x.ctot % 4) || (d.x.coff % 4) || (d.y.ctot % 4) || (d.y.coff % 4)) return no("views must be 4-channel aligned");
-        if (d.r1.ptr && ((d.r1.ctot % 4) || (d.r1.coff % 4) || (d.r1_ch % 4))) return no("r1 view");
-        if (d.r2.ptr && ((d.r2.ctot % 4) || (d.r2.coff % 4))) return no("r2 view");
-        if (d.m.ptr && ((d.m.ctot % 4) || (d.m.coff % 4) || (d.m_lo % 4) || (d.m_hi % 4))) return no("mask view");
+        if (!views_aligned(d)) return no("x / y / r1 / r2 / mask views must be 4-channel aligned");
         if (d.noise_pos < 0 || d.noise_pos > 2 || (i < 4 && d.noise_pos != 0)) return no("the noise multiplier belongs to the last stage");
-        if ((int64_t)d.N * d.H * d.W * d.x.ctot >= (1LL << 30) || (int64_t)d.N * d.H * d.W * d.y.ctot >= (1LL << 30)) return no("buffer above 4 GiB");
+        if (!buffers_addressable(d)) return no("buffer above 4 GiB");
         if (!d.x.ptr || !d.y.ptr || !d.wp) return no("null pointer");
     }
     const tnr_conv_desc &dl = st[n - 1];
@@ -1556,24 +1553,32 @@ int sweep_form() {
 }
 constexpr size_t S4D_LDS_BYTES = (size_t)(2 * SW_A_FLOATS) * sizeof(float);      // direct form: the input tile's double buffer only
 
+// CU count once the sweep kernels are set up, 0 when they cannot be (tnr_kernel_setup has the reason; tnr_conv_sweep_image_bytes
+// answers 0 then: that form is unavailable)
 int sweep_cus() {
     static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)SW_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)SW_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep4_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_sweep4_kernel<true, false, SwPlan4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)S4D_LDS_BYTES) != hipSuccess || cus < 1)
-            cus = -1;
-    }
+    tnr_kernel_setup(&cus, "conv_sweep", {{conv_sweep_kernel, SW_LDS_BYTES}, {conv_sweep4_kernel<false>, SW_LDS_BYTES},
+                                          {conv_sweep4_kernel<true>, S4D_LDS_BYTES}, {conv_sweep4_kernel<true, true>, S4D_LDS_BYTES},
+                                          {conv_sweep4_kernel<true, false, SwPlan4>, S4D_LDS_BYTES}});
     return cus;
+}
+
+// the pack kernel's arguments for a block that passed sweep_pattern; `who` prefixes the messages
+int sweep_pack_args(const char *who, const tnr_conv_desc *stages, int n, void *image, int64_t image_bytes, SweepPackK &a) {
+    a.nck0 = stages[0].Cin / 16;
+    a.ns = n;
+    a.units = sw_total_units(a.nck0, n);
+    a.direct = sweep_form() == 5;
+    TNR_REQUIRE((int64_t)a.units * SW_UNIT_FLOATS * (int64_t)sizeof(float) <= image_bytes, "%s: image buffer too small", who);
+    TNR_REQUIRE(n == SW_NSTAGE || a.direct, "%s: four stages run in the direct four-wave form only", who);
+    for (int i = 0; i < SW_NSTAGE; ++i) {
+        const tnr_conv_desc &d = stages[i < n ? i : n - 1];          // (four stages: the fifth entry is never read)
+        a.wp[i] = d.wp;
+        a.KinP[i] = d.KinP;
+        a.KoutP[i] = d.KoutP;
+    }
+    a.out = static_cast<float *>(image);
+    return TNR_OK;
 }
 
 }  // namespace
@@ -1610,19 +1615,7 @@ extern "C" int tnr_conv_sweep_pack(const tnr_conv_desc *stages, int32_t n, void 
     const char *why = "";
     TNR_REQUIRE(stages != nullptr && image != nullptr && sweep_pattern(stages, n, &why), "conv_sweep_pack: not a sweepable dense block (%s)", why);
     SweepPackK a;
-    a.nck0 = stages[0].Cin / 16;
-    a.ns = n;
-    a.units = sw_total_units(a.nck0, n);
-    a.direct = sweep_form() == 5;
-    TNR_REQUIRE((int64_t)a.units * SW_UNIT_FLOATS * (int64_t)sizeof(float) <= image_bytes, "conv_sweep_pack: image buffer too small");
-    TNR_REQUIRE(n == SW_NSTAGE || a.direct, "conv_sweep_pack: four stages run in the direct four-wave form only");
-    for (int i = 0; i < SW_NSTAGE; ++i) {
-        const tnr_conv_desc &d = stages[i < n ? i : n - 1];          // (four stages: the fifth entry is never read)
-        a.wp[i] = d.wp;
-        a.KinP[i] = d.KinP;
-        a.KoutP[i] = d.KoutP;
-    }
-    a.out = static_cast<float *>(image);
+    if (const int rc = sweep_pack_args("conv_sweep_pack", stages, n, image, image_bytes, a)) return rc;
     hipLaunchKernelGGL(sweep_pack_kernel, dim3((unsigned)tnr_cdiv(a.units * 64, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return tnr_check_launch("conv_sweep_pack");
 }
@@ -1634,19 +1627,7 @@ extern "C" int tnr_conv_sweep_pack_item(const tnr_conv_desc *stages, int32_t n, 
     TNR_REQUIRE(stages != nullptr && image != nullptr && item != nullptr && sweep_pattern(stages, n, &why),
                 "conv_sweep_pack_item: not a sweepable dense block (%s)", why);
     SweepPackK a;
-    a.nck0 = stages[0].Cin / 16;
-    a.ns = n;
-    a.units = sw_total_units(a.nck0, n);
-    a.direct = sweep_form() == 5;
-    TNR_REQUIRE((int64_t)a.units * SW_UNIT_FLOATS * (int64_t)sizeof(float) <= image_bytes, "conv_sweep_pack_item: image buffer too small");
-    TNR_REQUIRE(n == SW_NSTAGE || a.direct, "conv_sweep_pack_item: four stages run in the direct four-wave form only");
-    for (int i = 0; i < SW_NSTAGE; ++i) {
-        const tnr_conv_desc &d = stages[i < n ? i : n - 1];
-        a.wp[i] = d.wp;
-        a.KinP[i] = d.KinP;
-        a.KoutP[i] = d.KoutP;
-    }
-    a.out = static_cast<float *>(image);
+    if (const int rc = sweep_pack_args("conv_sweep_pack_item", stages, n, image, image_bytes, a)) return rc;
     memset(item, 0, sizeof(*item));
     memcpy(item->opaque, &a, sizeof(a));
     item->units = a.units;
@@ -1668,7 +1649,7 @@ extern "C" int tnr_conv_sweep(const tnr_conv_desc *stages, int32_t n, const void
     const tnr_conv_desc &d0 = stages[0];
     TNR_REQUIRE(tnr_conv_chain_workspace_bytes(&d0) <= ws_bytes, "conv_sweep: workspace too small");
     const int cus = sweep_cus();
-    TNR_REQUIRE(cus >= 1, "conv_sweep: cannot set up the kernel");
+    if (cus < 1) return TNR_ELAUNCH;
     SweepK c;
     c.nck0 = d0.Cin / 16;
     c.tiles_x = tnr_cdiv(d0.W, SW_TW);
@@ -1686,19 +1667,8 @@ extern "C" int tnr_conv_sweep(const tnr_conv_desc *stages, int32_t n, const void
     c.wq_bytes = sw_total_units(c.nck0, n) * SW_UNIT_FLOATS * (int)sizeof(float);
     for (int i = 0; i < SW_NSTAGE; ++i) {
         const tnr_conv_desc *d = &stages[i < n ? i : n - 1];         // (four stages: the fifth entry is never read)
-        ConvK &k = c.st[i];
-        k.x = d->x.ptr; k.x_ct = d->x.ctot; k.x_co = d->x.coff;
-        k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin;
-        k.wp = d->wp; k.KinP = d->KinP; k.KoutP = d->KoutP;
-        k.y = d->y.ptr; k.y_ct = d->y.ctot; k.y_co = d->y.coff; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-        k.bias = d->bias; k.act = d->act; k.slope = d->slope; k.alpha = d->alpha;
-        k.r1 = d->r1.ptr; k.r1_ct = d->r1.ctot; k.r1_co = d->r1.coff; k.r1_ch = d->r1_ch; k.beta1 = d->beta1;
-        k.r2 = d->r2.ptr; k.r2_ct = d->r2.ctot; k.r2_co = d->r2.coff; k.alpha2 = d->alpha2;
-        k.m = d->m.ptr; k.m_ct = d->m.ctot; k.m_co = d->m.coff; k.m_lo = d->m_lo; k.m_hi = d->m_hi; k.m_slope = d->m_slope;
-        k.noise_pos = d->noise_pos; k.noise_sigma = d->noise_sigma; k.noise_k0 = d->noise_key0; k.noise_k1 = d->noise_key1; k.noise_pix0 = d->noise_pix0;
+        ConvK &k = c.st[i] = conv_k_from_desc(*d);
         k.tiles_x = c.tiles_x; k.tiles_y = c.tiles_y; k.ncb = d->KoutP / 32;
-        k.th_space = d->Ho; k.tw_space = d->Wo;
-        k.ksplit = 1; k.split_stride = 0; k.bf = d->mma; k.reflect = 0;
     }
     // whole images per round of the grid, one tile per workgroup and round
     const int per_round = (cus / c.tpi) * c.tpi;
@@ -1752,42 +1722,12 @@ extern "C" int tnr_conv_wq_pack(const tnr_conv_desc *d, void *image, int64_t ima
 int tnr_launch_conv_s2_d4(const tnr_conv_desc *d, void *stream) {
     if (!s2_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wq_bytes(d) || d->noise_pos != 0) return 1;
     static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_s2_d4_kernel<TNR_CONV_4x4_S2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_s2_d4_kernel<TNR_CONV_4x4_S2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_s2_d4_kernel<TNR_DGRAD_4x4_S2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv_s2_d4_kernel<TNR_DGRAD_4x4_S2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess || cus < 1) {
-            cus = 0;
-            tnr_set_error("conv_s2_d4: cannot set up the kernel");
-            return TNR_ELAUNCH;
-        }
-    }
+    if (const int rc = tnr_kernel_setup(&cus, "conv_s2_d4", {{conv_s2_d4_kernel<TNR_CONV_4x4_S2, false>, S4D_LDS_BYTES}, {conv_s2_d4_kernel<TNR_CONV_4x4_S2, true>, S4D_LDS_BYTES},
+                                                             {conv_s2_d4_kernel<TNR_DGRAD_4x4_S2, false>, S4D_LDS_BYTES}, {conv_s2_d4_kernel<TNR_DGRAD_4x4_S2, true>, S4D_LDS_BYTES}}))
+        return rc;
     const bool dg = d->mode == TNR_DGRAD_4x4_S2;
     S2K c;
-    ConvK &k = c.a;
-    k.x = d->x.ptr; k.x_ct = d->x.ctot; k.x_co = d->x.coff;
-    k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin;
-    k.wp = d->wp; k.KinP = d->KinP; k.KoutP = d->KoutP;
-    k.y = d->y.ptr; k.y_ct = d->y.ctot; k.y_co = d->y.coff; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-    k.bias = d->bias; k.act = d->act; k.slope = d->slope; k.alpha = d->alpha;
-    k.r1 = d->r1.ptr; k.r1_ct = d->r1.ctot; k.r1_co = d->r1.coff; k.r1_ch = d->r1_ch; k.beta1 = d->beta1;
-    k.r2 = d->r2.ptr; k.r2_ct = d->r2.ctot; k.r2_co = d->r2.coff; k.alpha2 = d->alpha2;
-    k.m = d->m.ptr; k.m_ct = d->m.ctot; k.m_co = d->m.coff; k.m_lo = d->m_lo; k.m_hi = d->m_hi; k.m_slope = d->m_slope;
-    k.noise_pos = 0; k.noise_sigma = 0.f; k.noise_k0 = 0; k.noise_k1 = 0; k.noise_pix0 = 0;
-    k.th_space = dg ? d->H : d->Ho; k.tw_space = dg ? d->W : d->Wo;
-    k.ksplit = 1; k.split_stride = 0; k.bf = d->mma; k.reflect = 0;
-    c.wq = static_cast<const float *>(d->wq);
-    c.wq_bytes = (int)tnr_conv_wq_bytes(d);
-    c.nck = d->Cin / 16;
-    c.tiles_x = tnr_cdiv(k.tw_space, SW_TW);
-    c.tiles_y = tnr_cdiv(k.th_space, SW_TH);
-    c.ncb = d->Cout / 64;
-    const int64_t tiles = (int64_t)c.tiles_x * c.tiles_y * c.ncb * d->N * (dg ? 4 : 1);
-    if (tiles >= (1LL << 31)) return 1;
-    c.tiles = (int)tiles;
-    k.tiles_x = c.tiles_x; k.tiles_y = c.tiles_y; k.ncb = c.ncb;
+    if (!stream_k_from_desc(c, *d, tnr_conv_wq_bytes(d), SW_TW, SW_TH, dg ? 4 : 1)) return 1;
     const unsigned grid = (unsigned)(c.tiles < 2 * cus ? c.tiles : 2 * cus);
     const bool amp = d->mma == TNR_MMA_BF16;
     if (dg) {
@@ -1805,42 +1745,11 @@ int tnr_launch_conv3x3_d4(const tnr_conv_desc *d, void *stream) {
     if (!d4_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wq_bytes(d) || d->noise_pos < 0 || d->noise_pos > 2) return 1;
     static int occ = [] { const char *e = getenv("TNR_D4_OCC"); return e ? atoi(e) : 2; }();
     static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_d4_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_d4_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_d4_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_d4_kernel<2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_d4_kernel<2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S4D_LDS_BYTES) != hipSuccess || cus < 1) {
-            cus = 0;
-            tnr_set_error("conv3x3_d4: cannot set up the kernel");
-            return TNR_ELAUNCH;
-        }
-    }
+    if (const int rc = tnr_kernel_setup(&cus, "conv3x3_d4", {{conv3x3_d4_kernel<1>, S4D_LDS_BYTES}, {conv3x3_d4_kernel<2>, S4D_LDS_BYTES}, {conv3x3_d4_kernel<2, true>, S4D_LDS_BYTES},
+                                                             {conv3x3_d4_kernel<2, false, true>, S4D_LDS_BYTES}, {conv3x3_d4_kernel<2, true, true>, S4D_LDS_BYTES}}))
+        return rc;
     D4K c;
-    ConvK &k = c.a;
-    k.x = d->x.ptr; k.x_ct = d->x.ctot; k.x_co = d->x.coff;
-    k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin;
-    k.wp = d->wp; k.KinP = d->KinP; k.KoutP = d->KoutP;
-    k.y = d->y.ptr; k.y_ct = d->y.ctot; k.y_co = d->y.coff; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-    k.bias = d->bias; k.act = d->act; k.slope = d->slope; k.alpha = d->alpha;
-    k.r1 = d->r1.ptr; k.r1_ct = d->r1.ctot; k.r1_co = d->r1.coff; k.r1_ch = d->r1_ch; k.beta1 = d->beta1;
-    k.r2 = d->r2.ptr; k.r2_ct = d->r2.ctot; k.r2_co = d->r2.coff; k.alpha2 = d->alpha2;
-    k.m = d->m.ptr; k.m_ct = d->m.ctot; k.m_co = d->m.coff; k.m_lo = d->m_lo; k.m_hi = d->m_hi; k.m_slope = d->m_slope;
-    k.noise_pos = d->noise_pos; k.noise_sigma = d->noise_sigma; k.noise_k0 = d->noise_key0; k.noise_k1 = d->noise_key1; k.noise_pix0 = d->noise_pix0;
-    k.th_space = d->Ho; k.tw_space = d->Wo;
-    k.ksplit = 1; k.split_stride = 0; k.bf = d->mma; k.reflect = d->pad_mode == 1;
-    c.wq = static_cast<const float *>(d->wq);
-    c.wq_bytes = (int)tnr_conv_wq_bytes(d);
-    c.nck = d->Cin / 16;
-    c.tiles_x = tnr_cdiv(d->Wo, SW_TW);
-    c.tiles_y = tnr_cdiv(d->Ho, SW_TH);
-    c.ncb = d->Cout / 64;
-    const int64_t tiles = (int64_t)c.tiles_x * c.tiles_y * c.ncb * d->N;
-    if (tiles >= (1LL << 31)) return 1;
-    c.tiles = (int)tiles;
-    k.tiles_x = c.tiles_x; k.tiles_y = c.tiles_y; k.ncb = c.ncb;
+    if (!stream_k_from_desc(c, *d, tnr_conv_wq_bytes(d), SW_TW, SW_TH, 1)) return 1;
     const int slots = cus * (occ == 1 ? 1 : 2);
     const int grid = c.tiles < slots ? c.tiles : slots;
     if (d->shuffle == 2) {

@@ -93,16 +93,9 @@ int launch_conv_t(const ConvK &k, int tiles, hipStream_t s) {
     constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
     static_assert(lds <= 80 * 1024, "conv tile exceeds the 2-workgroups-per-CU LDS budget");
 #endif
-    static bool attr_done = false;
     auto fn = conv_tile_kernel<MODE, TW, NT, MT, BF>;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-            tnr_set_error("conv_tile: cannot raise dynamic LDS to %zu bytes", lds);
-            return TNR_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    static int cus = 0;
+    if (const int rc = tnr_kernel_setup(&cus, "conv_tile", {{fn, lds}})) return rc;
     hipLaunchKernelGGL(fn, dim3(tiles), dim3(256), lds, s, k);
     return tnr_check_launch("conv_tile");
 }
@@ -135,6 +128,30 @@ int conv_pick_tw(int sw, int sh) {
     return best;
 }
 
+// Tile grid of a launch, for tnr_conv_forward and tnr_conv_workspace_bytes alike (the split-K workspace is sized from `tiles`).
+struct ConvTileGeom {
+    int tw, th, nt;
+    bool big_m;
+    int tiles_x, tiles_y, ncb;
+    int64_t tiles;
+};
+ConvTileGeom conv_tile_geom(const tnr_conv_desc *d) {
+    const bool dg = d->mode == TNR_DGRAD_4x4_S2;
+    const int sh = dg ? d->H : d->Ho, sw = dg ? d->W : d->Wo;      // the tile space (conv_k_from_desc: th_space, tw_space)
+    ConvTileGeom g;
+    g.tw = conv_pick_tw(sw, sh);
+    g.nt = d->Cout > 32 ? 2 : 1;
+    // 32-cout 3x3 layers (the dense-block convs and their gradients): 4 M-tiles per wave (16x32 pixel
+    // tile) so the weight slab and the fixed per-workgroup costs are amortised like in the 64-cout kernel
+    g.big_m = (d->mode == TNR_CONV_3x3) && g.nt == 1 && g.tw == 32 && sh >= 16;
+    g.th = (g.big_m ? 512 : 256) / g.tw;
+    g.tiles_x = tnr_cdiv(sw, g.tw);
+    g.tiles_y = tnr_cdiv(sh, g.th);
+    g.ncb = tnr_cdiv(d->Cout, g.nt * 32);
+    g.tiles = (int64_t)g.tiles_x * g.tiles_y * g.ncb * d->N * (dg ? 4 : 1);
+    return g;
+}
+
 // Split-K factor of a launch.  Only plain epilogues (bias / activation / alpha) can be deferred to the reduce
 // launch, and only launches that leave most of the 512 workgroup slots empty while looping over >= 32 input
 // chunks are worth a second launch: the 512-channel discriminator layers at 16x16 and below.
@@ -164,75 +181,46 @@ extern "C" int tnr_conv_forward(const tnr_conv_desc *d, void *stream) {
     if (d->mode == TNR_CONV_7x7_C4)
         TNR_REQUIRE(d->x.ctot == 4 && d->x.coff == 0 && d->Cin == 4 && d->KinP == 208 && d->wq == nullptr && d->ws == nullptr && d->shuffle == 0,
                     "conv7x7_c4: needs an NHWC4 input view and a 7x7 C4 packing (no weight stream, no split-K)");
-    TNR_REQUIRE((d->x.ctot % 4) == 0 && (d->x.coff % 4) == 0 && (d->Cin % 4) == 0,
-                "conv: input view must be 4-channel aligned (ctot %d coff %d Cin %d)", d->x.ctot, d->x.coff, d->Cin);
+    TNR_REQUIRE(views_aligned(*d) && (d->Cin % 4) == 0,
+                "conv: x / y / r1 (+ r1_ch) / r2 / mask (+ range) views and Cin must be 4-channel aligned (x: ctot %d coff %d Cin %d)", d->x.ctot, d->x.coff, d->Cin);
     TNR_REQUIRE((d->KinP % TNR_CK) == 0 && (d->KoutP % 32) == 0, "conv: bad packed dims %d %d", d->KinP, d->KoutP);
     TNR_REQUIRE(d->Cin <= d->KinP && d->Cout <= d->KoutP, "conv: Cin/Cout exceed the packing");
+    // (not buffers_addressable: this entry bounds the input only, at 2^31 elements; the weight-stream launchers behind it ask for the
+    // 2^30 bound on both buffers themselves)
     TNR_REQUIRE((int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 31), "conv: input buffer above 2^31 elements needs 64-bit offsets");
-    TNR_REQUIRE((d->y.ctot % 4) == 0 && (d->y.coff % 4) == 0, "conv: output view must be 4-channel aligned");
-    TNR_REQUIRE(d->r1.ptr == nullptr || ((d->r1.ctot % 4) == 0 && (d->r1.coff % 4) == 0 && (d->r1_ch % 4) == 0),
-                "conv: r1 view / r1_ch must be 4-channel aligned");
-    TNR_REQUIRE(d->r2.ptr == nullptr || ((d->r2.ctot % 4) == 0 && (d->r2.coff % 4) == 0), "conv: r2 view must be 4-channel aligned");
-    TNR_REQUIRE(d->m.ptr == nullptr || ((d->m.ctot % 4) == 0 && (d->m.coff % 4) == 0 && (d->m_lo % 4) == 0 && (d->m_hi % 4) == 0),
-                "conv: mask view / range must be 4-channel aligned");
     TNR_REQUIRE(d->Cout % 4 == 0 || (d->r1.ptr == nullptr && d->r2.ptr == nullptr && d->m.ptr == nullptr && d->noise_pos == 0),
                 "conv: residual / mask / noise epilogues need Cout %% 4 == 0");
     TNR_REQUIRE(d->noise_pos >= 0 && d->noise_pos <= 2, "conv: bad noise_pos %d", d->noise_pos);
-    ConvK k;
-    k.x = d->x.ptr; k.x_ct = d->x.ctot; k.x_co = d->x.coff;
-    k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin;
-    k.wp = d->wp; k.KinP = d->KinP; k.KoutP = d->KoutP;
-    k.y = d->y.ptr; k.y_ct = d->y.ctot; k.y_co = d->y.coff; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-    k.bias = d->bias; k.act = d->act; k.slope = d->slope; k.alpha = d->alpha;
-    k.r1 = d->r1.ptr; k.r1_ct = d->r1.ctot; k.r1_co = d->r1.coff; k.r1_ch = d->r1_ch; k.beta1 = d->beta1;
-    k.r2 = d->r2.ptr; k.r2_ct = d->r2.ctot; k.r2_co = d->r2.coff; k.alpha2 = d->alpha2;
-    k.m = d->m.ptr; k.m_ct = d->m.ctot; k.m_co = d->m.coff; k.m_lo = d->m_lo; k.m_hi = d->m_hi; k.m_slope = d->m_slope;
-    k.noise_pos = d->noise_pos; k.noise_sigma = d->noise_sigma; k.noise_k0 = d->noise_key0; k.noise_k1 = d->noise_key1; k.noise_pix0 = d->noise_pix0;
-
-    int sh, sw;  // tile space
     switch (d->mode) {
         case TNR_CONV_3x3:
         case TNR_CONV_1x1:
         case TNR_CONV_3x3_C4:
         case TNR_CONV_7x7_C4:
             TNR_REQUIRE(d->Ho == d->H && d->Wo == d->W, "conv3x3 / conv1x1 / conv7x7_c4: output must match input size");
-            sh = d->Ho; sw = d->Wo;
             break;
         case TNR_CONV_3x3_UP2:
             TNR_REQUIRE(d->Ho == 2 * d->H && d->Wo == 2 * d->W, "conv3x3_up2: output must be 2x input");
-            sh = d->Ho; sw = d->Wo;
             break;
         case TNR_CONV_4x4_S2:
             TNR_REQUIRE(2 * d->Ho == d->H && 2 * d->Wo == d->W, "conv4x4s2: output must be input/2");
-            sh = d->Ho; sw = d->Wo;
             break;
         default:  // TNR_DGRAD_4x4_S2
             TNR_REQUIRE(d->Ho == 2 * d->H && d->Wo == 2 * d->W, "dgrad4x4s2: output must be 2x gout size");
-            sh = d->H; sw = d->W;
             break;
     }
-    k.th_space = sh; k.tw_space = sw;
-    const int tw = conv_pick_tw(sw, sh);
-    const int nt = d->Cout > 32 ? 2 : 1;
-    // 32-cout 3x3 layers (the dense-block convs and their gradients): 4 M-tiles per wave (16x32 pixel
-    // tile) so the weight slab and the fixed per-workgroup costs are amortised like in the 64-cout kernel
-    const bool big_m = (d->mode == TNR_CONV_3x3) && nt == 1 && tw == 32 && sh >= 16;
-    const int th = (big_m ? 512 : 256) / tw;
-    k.tiles_x = tnr_cdiv(sw, tw);
-    k.tiles_y = tnr_cdiv(sh, th);
-    k.ncb = tnr_cdiv(d->Cout, nt * 32);
-    int64_t tiles = (int64_t)k.tiles_x * k.tiles_y * k.ncb * d->N * (d->mode == TNR_DGRAD_4x4_S2 ? 4 : 1);
+    ConvK k = conv_k_from_desc(*d);
+    const ConvTileGeom g = conv_tile_geom(d);
+    const int tw = g.tw, nt = g.nt, sh = k.th_space;
+    const bool big_m = g.big_m;
+    k.tiles_x = g.tiles_x; k.tiles_y = g.tiles_y; k.ncb = g.ncb;
+    int64_t tiles = g.tiles;
     TNR_REQUIRE(tiles > 0 && tiles < (1LL << 31), "conv: grid too large");
     hipStream_t s = (hipStream_t)stream;
     // split-K for launches that cannot fill the chip (see tnr_conv_workspace_bytes)
     const int ksplit = conv_ksplit(d, tiles);
     TNR_REQUIRE(d->mma >= TNR_MMA_F32 && d->mma <= TNR_MMA_BF16X3, "conv: bad mma %d", d->mma);
-    k.bf = d->mma;
-    k.reflect = d->pad_mode == 1;
     TNR_REQUIRE(d->pad_mode == 0 || (d->pad_mode == 1 && d->mode == TNR_CONV_3x3 && d->H >= 2 && d->W >= 2) ||
                 (d->pad_mode == 1 && d->mode == TNR_CONV_7x7_C4 && d->H >= 4 && d->W >= 4), "conv: pad_mode 1 (reflection) is for TNR_CONV_3x3 and TNR_CONV_7x7_C4");
-    k.ksplit = 1;
-    k.split_stride = 0;
     SplitRedK red;
     if (ksplit > 1 && d->ws != nullptr) {
         const int64_t plane = (int64_t)d->N * d->Ho * d->Wo * k.KoutP;
@@ -299,14 +287,6 @@ extern "C" int tnr_conv_forward(const tnr_conv_desc *d, void *stream) {
 
 extern "C" int64_t tnr_conv_workspace_bytes(const tnr_conv_desc *d) {
     if (d == nullptr) return 0;
-    int sh = d->Ho, sw = d->Wo;
-    if (d->mode == TNR_DGRAD_4x4_S2) { sh = d->H; sw = d->W; }
-    const int tw = conv_pick_tw(sw, sh);
-    const int nt = d->Cout > 32 ? 2 : 1;
-    const bool big_m = (d->mode == TNR_CONV_3x3) && nt == 1 && tw == 32 && sh >= 16;
-    const int th = (big_m ? 512 : 256) / tw;
-    const int64_t tiles = (int64_t)tnr_cdiv(sw, tw) * tnr_cdiv(sh, th) * tnr_cdiv(d->Cout, nt * 32) * d->N *
-                          (d->mode == TNR_DGRAD_4x4_S2 ? 4 : 1);
-    const int ks = conv_ksplit(d, tiles);
+    const int ks = conv_ksplit(d, conv_tile_geom(d).tiles);
     return ks > 1 ? (int64_t)ks * d->N * d->Ho * d->Wo * tnr_round_up(d->Cout, 32) * (int64_t)sizeof(float) : 0;
 }

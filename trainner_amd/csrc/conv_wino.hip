@@ -726,8 +726,7 @@ __global__ void __launch_bounds__(1024, 4) conv3x3_wino16_kernel(const WinoK c) 
 bool wino_ok(const tnr_conv_desc *d) {
     return d->mode == TNR_CONV_3x3 && d->mma == TNR_MMA_BF16X3 && (d->pad_mode == 0 || (d->pad_mode == 1 && d->H >= 2 && d->W >= 2)) &&
            (d->Cout % 64) == 0 && d->KoutP == d->Cout && d->Cin == d->KinP && (d->Cin % 16) == 0 && d->Cin >= 32 && d->Ho == d->H &&
-           d->Wo == d->W && d->W >= 8 && d->H >= 8 && (int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 30) &&
-           (int64_t)d->N * d->H * d->W * d->y.ctot < (1LL << 30) &&
+           d->Wo == d->W && d->W >= 8 && d->H >= 8 && buffers_addressable(*d) &&
            (int64_t)(d->Cout / 64) * (d->Cin / 16) * 32 * WN_UNIT_FLOATS * (int64_t)sizeof(float) < (1LL << 31);
 }
 
@@ -764,40 +763,9 @@ extern "C" int tnr_conv_wino_pack(const tnr_conv_desc *d, void *image, int64_t i
 int tnr_launch_conv3x3_wino(const tnr_conv_desc *d, void *stream) {
     if (!wino_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wino_bytes(d) || d->noise_pos < 0 || d->noise_pos > 2) return 1;
     static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wino_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WN_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wino16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WN_LDS_BYTES) != hipSuccess ||
-            cus < 1) {
-            cus = 0;
-            tnr_set_error("conv3x3_wino: cannot set up the kernel");
-            return TNR_ELAUNCH;
-        }
-    }
+    if (const int rc = tnr_kernel_setup(&cus, "conv3x3_wino", {{conv3x3_wino_kernel, WN_LDS_BYTES}, {conv3x3_wino16_kernel, WN_LDS_BYTES}})) return rc;
     WinoK c;
-    ConvK &k = c.a;
-    k.x = d->x.ptr; k.x_ct = d->x.ctot; k.x_co = d->x.coff;
-    k.N = d->N; k.H = d->H; k.W = d->W; k.Cin = d->Cin;
-    k.wp = d->wp; k.KinP = d->KinP; k.KoutP = d->KoutP;
-    k.y = d->y.ptr; k.y_ct = d->y.ctot; k.y_co = d->y.coff; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-    k.bias = d->bias; k.act = d->act; k.slope = d->slope; k.alpha = d->alpha;
-    k.r1 = d->r1.ptr; k.r1_ct = d->r1.ctot; k.r1_co = d->r1.coff; k.r1_ch = d->r1_ch; k.beta1 = d->beta1;
-    k.r2 = d->r2.ptr; k.r2_ct = d->r2.ctot; k.r2_co = d->r2.coff; k.alpha2 = d->alpha2;
-    k.m = d->m.ptr; k.m_ct = d->m.ctot; k.m_co = d->m.coff; k.m_lo = d->m_lo; k.m_hi = d->m_hi; k.m_slope = d->m_slope;
-    k.noise_pos = d->noise_pos; k.noise_sigma = d->noise_sigma; k.noise_k0 = d->noise_key0; k.noise_k1 = d->noise_key1; k.noise_pix0 = d->noise_pix0;
-    k.th_space = d->Ho; k.tw_space = d->Wo;
-    k.ksplit = 1; k.split_stride = 0; k.bf = d->mma; k.reflect = d->pad_mode == 1;
-    c.wq = static_cast<const float *>(d->wq);
-    c.wq_bytes = (int)tnr_conv_wino_bytes(d);
-    c.nck = d->Cin / 16;
-    c.tiles_x = tnr_cdiv(d->Wo, WN_T);
-    c.tiles_y = tnr_cdiv(d->Ho, WN_T);
-    c.ncb = d->Cout / 64;
-    const int64_t tiles = (int64_t)c.tiles_x * c.tiles_y * c.ncb * d->N;
-    if (tiles >= (1LL << 31)) return 1;
-    c.tiles = (int)tiles;
-    k.tiles_x = c.tiles_x; k.tiles_y = c.tiles_y; k.ncb = c.ncb;
+    if (!stream_k_from_desc(c, *d, tnr_conv_wino_bytes(d), WN_T, WN_T, 1)) return 1;
     const int grid = c.tiles < cus ? c.tiles : cus;
     static const bool w16 = [] { const char *e = getenv("TNR_WINO_WAVES"); return e != nullptr && atoi(e) == 16; }();
     if (w16) {

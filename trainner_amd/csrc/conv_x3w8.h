@@ -167,15 +167,8 @@ inline int launch_conv3x3_x3w8(ConvK k, hipStream_t s) {
     k.tiles_y = tnr_cdiv(k.th_space, G::TH);
     k.ncb = tnr_cdiv(k.Cout, G::NC);
     const int64_t tiles = (int64_t)k.tiles_x * k.tiles_y * k.ncb * k.N;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_x3w8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)G::LDS_BYTES) != hipSuccess) {
-            tnr_set_error("conv3x3_x3w8: cannot raise dynamic LDS to %zu bytes", G::LDS_BYTES);
-            return TNR_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    static int cus = 0;
+    if (const int rc = tnr_kernel_setup(&cus, "conv3x3_x3w8", {{conv3x3_x3w8_kernel, G::LDS_BYTES}})) return rc;
     hipLaunchKernelGGL(conv3x3_x3w8_kernel, dim3((unsigned)tiles), dim3(512), G::LDS_BYTES, s, k);
     return tnr_check_launch("conv3x3_x3w8");
 }

@@ -1055,16 +1055,9 @@ int launch_wgrad_t(const WgK &k, int jobs, hipStream_t s) {
     } else {
     // (TNR_MMA_BF16X3 classes inherited from the fp32 plan may exceed 80 KB: the LDS then limits them to one workgroup per CU)
     static_assert(lds <= ((one_wg || BF == 2) ? 160 : 80) * 1024, "wgrad tile exceeds the LDS budget of its occupancy regime");
-    static bool attr_done = false;
     auto fn = wgrad_tile_kernel<MODE, A_T, B_T, THG, BF, WPS, DB>;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-            tnr_set_error("wgrad_tile: cannot raise dynamic LDS to %zu bytes", lds);
-            return TNR_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    static int cus = 0;
+    if (const int rc = tnr_kernel_setup(&cus, "wgrad_tile", {{fn, lds}})) return rc;
     hipLaunchKernelGGL(fn, dim3(k.nsplits, jobs, 1), dim3(256), lds, s, k);
     return tnr_check_launch("wgrad_tile");
     }
