@@ -318,6 +318,11 @@ int tnr_conv_wgrad(const tnr_wgrad_desc *d, void *stream);
  * the summation order of the split-K partials (still run-to-run deterministic).                     */
 #define TNR_WGRAD_GROUP_MAX 12
 int tnr_conv_wgrad_group(const tnr_wgrad_desc *descs, int32_t n, void *stream);
+/* Host-only query, no device and no launch: the workgroup tile class tnr_conv_wgrad_group runs `d` on when its launch carries group_jobs
+ * (cin block, cout block) jobs (0: the layer alone).  x3_occ: the value of TNR_WG_X3_OCC to plan for, < 0: the process's setting.
+ * out = {mode, A_T, B_T, THG, BF, WPS, DB (the kernel's template arguments), KS, splits, tiles_per_split, LDS bytes, index of the class in
+ * the library's table}.  Only d's shape fields, mode, mma, pad_mode and the views' ctot are read.  TNR_EINVAL: no kernel for this descriptor. */
+int tnr_wgrad_tile_class(const tnr_wgrad_desc *d, int32_t group_jobs, int32_t x3_occ, int32_t out[12]);
 
 /* --- image-to-image family (Pix2Pix / CycleGAN: ResnetGenerator ResNet_arch.py:11-90, NLayerDiscriminator
  * discriminators.py:472-579).  Generic convolution on the vector ALUs for the layers outside the matrix-core geometries

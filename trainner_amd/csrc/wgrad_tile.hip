@@ -9,6 +9,7 @@
 // and wgrad_reduce sums the slabs in a fixed order (deterministic split-K) into the OIHW gradient.
 // The 4x4 s2 convolution is handled in its space-to-depth form (2x2 taps over 4*Cin virtual
 // channels), exactly like conv_tile.hip.
+#include <array>
 #include <type_traits>
 #include <utility>
 #include "common.h"
@@ -52,7 +53,6 @@ struct WgCfg {
     static constexpr int KS = (NTAPS_ == 9 && (AB == 1 || AB == 2)) ? 4 / AB : 1;
     static constexpr int WPG = 4 / KS;                       // waves per pixel group
     static constexpr int J = (AB * NTAPS_ + WPG - 1) / WPG;
-    static constexpr bool PIPE = true;
     static constexpr int WAVES_PER_SIMD = (J >= 9) ? 1 : 2;
 };
 
@@ -72,9 +72,6 @@ __device__ __forceinline__ void wg_pk_level(const f32x4 x, wg_bf16x4 &pk, f32x4 
                         __builtin_bit_cast(float, p1 << 16), __builtin_bit_cast(float, p1 & 0xffff0000u)};
     res = x - back;
 }
-#ifndef WG_PK_SPLIT
-#define WG_PK_SPLIT 1       /* 0: the split through __builtin_convertvector (30 instead of 22 vector instructions per item; bit-identical) */
-#endif
 typedef __attribute__((address_space(3))) wg_s16x4 wg_lds_s16x4;
 
 // ---- TNR_MMA_BF16X3: the LDS image is PRE-SPLIT -- three bf16 planes (hi, mid, lo) written once by the stager -- and pixel-major,
@@ -123,13 +120,10 @@ wgrad_tile_kernel(const WgK ga) {
     constexpr int T = AB * NTAPS, J = WgCfg<A_T, B_T, NTAPS>::J;
     constexpr int ROWS = THG / KS;                           // pixel rows of the tile one wave group reduces over
     static_assert(THG % KS == 0, "tile rows must split evenly over the pixel groups");
-#ifdef TNR_WG_X3_PIPE2
-    constexpr bool PIPE = WgCfg<A_T, B_T, NTAPS>::PIPE;
-#else
+    // PIPE: the loads of tile i+1 fly during the MFMA phase of tile i
     // (TNR_MMA_BF16X3 with two workgroups per CU: the staging registers of an in-flight next tile do not fit next to 144 accumulators
     //  in 256 registers -- the tile is loaded at its start instead, under the OTHER workgroup's MFMA phase)
-    constexpr bool PIPE = WgCfg<A_T, B_T, NTAPS>::PIPE && !(BF == 2 && WPS == 2 && WgCfg<A_T, B_T, NTAPS>::J >= 9);
-#endif
+    constexpr bool PIPE = !(BF == 2 && WPS == 2 && J >= 9);
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *s_g = smem;             // PX * COB
@@ -269,22 +263,10 @@ wgrad_tile_kernel(const WgK ga) {
         const TileAt ta = tile_at(tile);
         wg_static_for<0, BATCH>([&](auto kc) __attribute__((always_inline)) { load_item(ta, batch, kc); });
     };
-    // PIPE: the loads of tile i+1 fly during the MFMA phase of tile i, issued as one burst in front of it.  Handing them out over
-    // the first MFMA groups instead (what pays in conv_body.h: -3 % per dense-block chain) was measured here and LOSES: grouped
-    // 32-cout jobs 104 -> 134 us, 192 -> 64: 491 -> 518 us, weight gradients 99 -> 116 ms per step (the staging index arithmetic
-    // moves into the k-loop; the 256-register classes spill).  Kept behind -DTNR_WG_SPREAD_ALL for the record.
-#if defined(TNR_WG_SPREAD_ALL) && !defined(TNR_NO_LOAD_SPREAD)
-    constexpr bool SPREAD = PIPE;
-#else
-    constexpr bool SPREAD = false;
-#endif
-    constexpr int SPREAD_N = 3, IPG = (BATCH + SPREAD_N - 1) / SPREAD_N;
-    auto load_group = [&](int tile, auto gc) __attribute__((always_inline)) {          // group g of SPREAD_N: items [g IPG, (g + 1) IPG) of batch 0
-        constexpr int g = decltype(gc)::value;
-        constexpr int k0 = g * IPG < BATCH ? g * IPG : BATCH, k1 = (g + 1) * IPG < BATCH ? (g + 1) * IPG : BATCH;
-        const TileAt ta = tile_at(tile);
-        wg_static_for<k0, k1>([&](auto kc) __attribute__((always_inline)) { load_item(ta, 0, kc); });
-    };
+    // PIPE: the loads of tile i+1 are issued as one burst in front of the MFMA phase of tile i.  Handing them out over the first MFMA
+    // groups instead (what pays in conv_body.h: -3 % per dense-block chain) was measured here and LOSES: grouped 32-cout jobs
+    // 104 -> 134 us, 192 -> 64: 491 -> 518 us, weight gradients 99 -> 116 ms per step (the staging index arithmetic moves into the
+    // k-loop; the 256-register classes spill).
     auto split4 = [&](const f32x4 v, wg_f32x2 (&out)[3]) {
         wg_bf16x4 h, m, l;
 #pragma unroll
@@ -435,30 +417,16 @@ wgrad_tile_kernel(const WgK ga) {
         auto item_step = [&](auto kc, auto sc, char *set) __attribute__((always_inline)) {
             constexpr int k = decltype(kc)::value, st = decltype(sc)::value;
             if constexpr (st == 0) {
-#if WG_PK_SPLIT
                 wg_pk_level(rr[k], ih, ir);
-#else
-                ih = __builtin_convertvector(rr[k], wg_bf16x4);
-                ir = rr[k] - __builtin_convertvector(ih, f32x4);
-#endif
             } else if constexpr (st == 1) {
-#if WG_PK_SPLIT
                 const f32x4 r1 = ir;
                 wg_pk_level(r1, im, ir);
-#else
-                im = __builtin_convertvector(ir, wg_bf16x4);
-                ir = ir - __builtin_convertvector(im, f32x4);
-#endif
             } else {
-#if WG_PK_SPLIT
                 if constexpr (st == 2) {
                     const wg_f32x2 a = {ir[0], ir[1]}, b = {ir[2], ir[3]};
                     il = __builtin_bit_cast(wg_bf16x4, wg_f32x2{__builtin_bit_cast(float, __builtin_convertvector(a, wg_bf16x2)),
                                                                 __builtin_bit_cast(float, __builtin_convertvector(b, wg_bf16x2))});
                 }
-#else
-                if constexpr (st == 2) il = __builtin_convertvector(ir, wg_bf16x4);
-#endif
                 *reinterpret_cast<wg_f32x2 *>(set + it_dst[k] + 256 * (st - 2)) = __builtin_bit_cast(wg_f32x2, st == 2 ? ih : (st == 3 ? im : il));
             }
         };
@@ -598,7 +566,6 @@ wgrad_tile_kernel(const WgK ga) {
                             else if constexpr (m < 24 && r + 1 < ROWS) read_a(std::integral_constant<int, (r + 1 < ROWS ? r + 1 : r)>{}, std::integral_constant<int, (m >= 18 && m < 24 ? m - 18 : 0)>{});
                         }
                         // the next pixel tile: loads behind every second MFMA from the start, item steps in the tail of the phase
-#ifndef WG_ABL_NOITEMS       /* (ablation builds: timing only, results invalid) */
                         if constexpr ((g & 1) == 0 && g / 2 < N_IT) {
                             item_load(std::integral_constant<int, (g / 2 < N_IT ? g / 2 : 0)>{});
                         }
@@ -606,7 +573,6 @@ wgrad_tile_kernel(const WgK ga) {
                             item_step(std::integral_constant<int, (g >= G0 && g < G0 + 5 * N_IT ? (g - G0) / 5 : 0)>{},
                                       std::integral_constant<int, (g >= G0 ? (g - G0) % 5 : 0)>{}, oset);
                         }
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 });
@@ -620,7 +586,7 @@ wgrad_tile_kernel(const WgK ga) {
                 __syncthreads();  // previous tile's fragments are consumed
                 store_batch(0);
                 __syncthreads();
-                if (!SPREAD && tile + 1 < t_end) load_batch(tile + 1, 0);  // in flight during the MFMA phase below
+                if (tile + 1 < t_end) load_batch(tile + 1, 0);  // in flight during the MFMA phase below
             } else {
                 load_batch(tile, 0);
                 __syncthreads();
@@ -745,17 +711,6 @@ wgrad_tile_kernel(const WgK ga) {
     #pragma unroll
                         for (int j = 0; j < J; ++j) xo[j] += WT * CIB;
                         if (r + 1 < ROWS) read_row();
-                        if constexpr (SPREAD) {
-                            if (tile + 1 < t_end) {
-                                if constexpr (ROWS >= SPREAD_N) {
-                                    if (r == 0) load_group(tile + 1, std::integral_constant<int, 0>{});
-                                    if (r == 1) load_group(tile + 1, std::integral_constant<int, 1>{});
-                                    if (r == 2) load_group(tile + 1, std::integral_constant<int, 2>{});
-                                } else if (r == 0) {
-                                    load_batch(tile + 1, 0);
-                                }
-                            }
-                        }
                         __builtin_amdgcn_sched_barrier(0);
     #pragma unroll
                         for (int j = 0; j < J; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ca, cb[j], acc[j], 0, 0, 0);
@@ -778,13 +733,6 @@ wgrad_tile_kernel(const WgK ga) {
                         fa[nxt] = smem[go + goff];
     #pragma unroll
                         for (int j = 0; j < J; ++j) fb[nxt][j] = smem[xo[j] + xoff];
-                        if constexpr (SPREAD) {
-                            if (r == 0 && tile + 1 < t_end) {
-                                if (k == 0) load_group(tile + 1, std::integral_constant<int, 0>{});
-                                if (k == 1) load_group(tile + 1, std::integral_constant<int, 1>{});
-                                if (k == 2) load_group(tile + 1, std::integral_constant<int, 2>{});
-                            }
-                        }
                         __builtin_amdgcn_sched_barrier(0);
                         bsum += fa[cur];
     #pragma unroll
@@ -964,148 +912,148 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const RedK ga) {
     }
 }
 
+// ---- Tile classes.  One row per instantiation of wgrad_tile_kernel: exactly the classes some descriptor reaches under some TNR_WG_X3_OCC
+// (tests/test_cpu_wgrad_plan.py).  plan_wgrad names a row, the LDS size and the slab geometry are computed from the row, and the launch walks
+// the table, so a kernel is instantiated only for a row and a plan can only run the kernel it sized its slabs for.
+struct WgRow { int mode, a_t, b_t, thg, bf, wps; bool db; };
+constexpr bool operator==(const WgRow &a, const WgRow &b) {
+    return a.mode == b.mode && a.a_t == b.a_t && a.b_t == b.b_t && a.thg == b.thg && a.bf == b.bf && a.wps == b.wps && a.db == b.db;
+}
+constexpr int M3 = TNR_CONV_3x3, MU = TNR_CONV_3x3_UP2, MS = TNR_CONV_4x4_S2;
+constexpr WgRow WG_ROWS[] = {
+    // fp32 and bf16, the 3x3 modes: 32x32, 32x64, 64x32 pixel-split over 16-row tiles; 32x96 (4 rows, two workgroups per CU); 32x128, 64x64
+    {M3, 1, 1, 16, 0, 1}, {M3, 1, 2, 16, 0, 1}, {M3, 1, 3, 4, 0, 2}, {M3, 1, 4, 8, 0, 1}, {M3, 2, 1, 16, 0, 1}, {M3, 2, 2, 8, 0, 1},
+    {M3, 1, 1, 16, 1, 1}, {M3, 1, 2, 16, 1, 1}, {M3, 1, 3, 4, 1, 2}, {M3, 1, 4, 8, 1, 1}, {M3, 2, 1, 16, 1, 1}, {M3, 2, 2, 8, 1, 1},
+    {MU, 1, 1, 16, 0, 1}, {MU, 1, 2, 16, 0, 1}, {MU, 1, 3, 4, 0, 2}, {MU, 1, 4, 8, 0, 1}, {MU, 2, 1, 16, 0, 1}, {MU, 2, 2, 8, 0, 1},
+    {MU, 1, 1, 16, 1, 1}, {MU, 1, 2, 16, 1, 1}, {MU, 1, 3, 4, 1, 2}, {MU, 1, 4, 8, 1, 1}, {MU, 2, 1, 16, 1, 1}, {MU, 2, 2, 8, 1, 1},
+    // TNR_MMA_BF16X3, the 3x3 modes.  32x96 at every TNR_WG_X3_OCC; then TNR_WG_X3_OCC=1: the fp32 classes, 32x64 at half height (the
+    // pre-split image takes 6 bytes per element: 16 rows would not fit the 160 KB)
+    {M3, 1, 3, 4, 2, 2}, {M3, 1, 1, 16, 2, 1}, {M3, 1, 2, 8, 2, 1}, {M3, 1, 4, 8, 2, 1}, {M3, 2, 1, 16, 2, 1}, {M3, 2, 2, 8, 2, 1},
+    {MU, 1, 3, 4, 2, 2}, {MU, 1, 1, 16, 2, 1}, {MU, 1, 2, 8, 2, 1}, {MU, 1, 4, 8, 2, 1}, {MU, 2, 1, 16, 2, 1}, {MU, 2, 2, 8, 2, 1},
+    // TNR_WG_X3_OCC >= 2: half-height tiles, two workgroups per CU
+    {M3, 1, 1, 8, 2, 2}, {M3, 1, 2, 4, 2, 2}, {M3, 2, 1, 4, 2, 2}, {M3, 2, 2, 4, 2, 2},
+    {MU, 1, 1, 8, 2, 2}, {MU, 1, 2, 4, 2, 2}, {MU, 2, 1, 4, 2, 2}, {MU, 2, 2, 4, 2, 2},
+    // TNR_WG_X3_OCC=3 (default), zero-padded 3x3 below 2^30 elements: the pipelined one-workgroup form with two tile sets
+    {M3, 1, 1, 8, 2, 1, true}, {M3, 1, 2, 4, 2, 1, true}, {M3, 2, 1, 4, 2, 1, true}, {M3, 2, 2, 4, 2, 1, true},
+    // 4x4 s2 (four virtual 32-channel blocks per 32 input channels): 32x128 and 64x64, two workgroups per CU; the last row is TNR_MMA_BF16X3
+    // with TNR_WG_X3_OCC >= 2 (the 8-row pre-split image is 109 KB: one workgroup per CU and nothing hides the refill; 4 rows: 58 KB, two)
+    {MS, 1, 4, 4, 0, 2}, {MS, 2, 2, 8, 0, 2}, {MS, 1, 4, 4, 1, 2}, {MS, 2, 2, 8, 1, 2}, {MS, 1, 4, 4, 2, 2}, {MS, 2, 2, 8, 2, 2}, {MS, 2, 2, 4, 2, 2},
+};
+constexpr int WG_NROWS = sizeof(WG_ROWS) / sizeof(WG_ROWS[0]);
+
+// LDS bytes of a class: its tile image, or the pixel-group exchange (ks > 1; wpg waves of j accumulators per group) where that is larger
+constexpr size_t wg_lds_bytes(const WgRow &r, int ks, int wpg, int j) {
+    const int kh = r.mode == TNR_CONV_4x4_S2 ? 2 : 3;
+    const size_t g = (size_t)r.thg * 16 * 32 * r.a_t, cib = 32 * r.b_t;
+    const size_t tile =
+        r.db ? 2 * ((g + (size_t)(r.thg + kh - 1) * 20 * cib) * 6 + 3072)              // two tile sets (halo rows of 20 pixels) + their dump areas
+        : r.bf == 2 ? (g + (size_t)(((r.thg + kh - 1) * (16 + kh - 1) + 3) / 4) * 4 * cib) * 6      // three bf16 planes, pixels in blocks of 4 (wg_x3_off)
+                    : (g + (size_t)(r.thg + kh) * (16 + kh - 1) * cib) * sizeof(float);      // + one halo row: the k-loop's last prefetch reads one row past the x tile (never consumed)
+    const size_t red = ks > 1 ? (size_t)(wpg * j * 16 * 64 + wpg * 64) * sizeof(float) : 0;
+    return tile > red ? tile : red;
+}
+
+struct WgRowInfo { int ks; size_t lds; };
+template <int I>
+constexpr WgRowInfo wg_row_info() {
+    constexpr WgRow r = WG_ROWS[I];
+    using Cfg = WgCfg<r.a_t, r.b_t, (r.mode == TNR_CONV_4x4_S2 ? 4 : 9)>;
+    constexpr size_t lds = wg_lds_bytes(r, Cfg::KS, Cfg::WPG, Cfg::J);
+    // WgCfg picks the workgroups per CU, except for the half-height TNR_MMA_BF16X3 classes.  Two workgroups per CU share the 160 KB; a
+    // TNR_MMA_BF16X3 class inherited from the fp32 plan may exceed 80 KB: the LDS then limits it to one workgroup per CU.
+    static_assert(r.wps == Cfg::WAVES_PER_SIMD || (r.bf == 2 && !r.db), "workgroups per CU differ from WgCfg's");
+    static_assert(lds <= ((r.wps == 1 || r.bf == 2) ? 160 : 80) * 1024, "wgrad tile exceeds the LDS budget of its occupancy regime");
+    return {Cfg::KS, lds};
+}
+template <int... I>
+constexpr std::array<WgRowInfo, sizeof...(I)> wg_row_infos(std::integer_sequence<int, I...>) { return {wg_row_info<I>()...}; }
+constexpr auto WG_INFO = wg_row_infos(std::make_integer_sequence<int, WG_NROWS>{});
+
 struct WgPlan {
-    int a_t, b_t, thg, ks, wps, db;
+    int row;                      // index into WG_ROWS
     int ncib, ncob;
     int KoutP, KinVP, cinp32;
     int tiles_x, tiles_y, tiles_total, splits, tiles_per_split;
-    int ntaps, resident;
+    int ntaps;
     int64_t ws_floats, db_floats;
 };
 
-// Tile class and slab geometry of one layer; the split count is chosen for `group_jobs` (cin block, cout
-// block) pairs sharing the launch (0: this layer alone).
-int plan_wgrad(const tnr_wgrad_desc *d, WgPlan &p, int group_jobs) {
+// The tile class of one layer, decided top-down: the first rule that matches names the class.  x3_occ: TNR_WG_X3_OCC.
+WgRow wgrad_class(const tnr_wgrad_desc *d, int x3_occ) {
+    const int m = d->mode, bf = d->mma;
+    const bool wide = d->Cout > 32;
+    const int cin_blocks = tnr_cdiv(d->Cin, 32);
+    if (m == TNR_CONV_4x4_S2) {                  // 4 * cin_blocks virtual blocks: always a full 128- or 64-wide job
+        if (!wide) return {m, 1, 4, 4, bf, 2};
+        return {m, 2, 2, (bf == TNR_MMA_BF16X3 && x3_occ >= 2) ? 4 : 8, bf, 2};
+    }
+    if (!wide && (cin_blocks == 3 || cin_blocks == 5)) return {m, 1, 3, 4, bf, 2};      // (the caller normally splits 160 = 96 + 64 itself)
+    const int a_t = wide ? 2 : 1;
+    if (bf == TNR_MMA_BF16X3 && x3_occ >= 2) {
+        // half-height tiles of at most 64 input channels (32 x 128 jobs become two 32 x 64 jobs: the 128-wide halo tile alone is 95 KB):
+        // <= 66 KB of pre-split LDS image per tile set, >= 2 tile rows per pixel group
+        const int b_t = cin_blocks >= 2 ? 2 : 1, thg = a_t * b_t == 1 ? 8 : 4;
+        const bool pipelined = x3_occ == 3 && m == TNR_CONV_3x3 && d->pad_mode == 0 &&
+                               (int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 30) && (int64_t)d->N * d->Ho * d->Wo * d->g.ctot < (1LL << 30);
+        return {m, a_t, b_t, thg, bf, pipelined ? 1 : 2, pipelined};
+    }
+    if (wide) return cin_blocks >= 2 ? WgRow{m, 2, 2, 8, bf, 1} : WgRow{m, 2, 1, 16, bf, 1};
+    if (cin_blocks == 1) return {m, 1, 1, 16, bf, 1};
+    if (cin_blocks == 2) return {m, 1, 2, bf == TNR_MMA_BF16X3 ? 8 : 16, bf, 1};
+    return {m, 1, 4, 8, bf, 1};
+}
+
+// Tile class and slab geometry of one layer; the split count is chosen for `group_jobs` (cin block, cout block) pairs sharing the launch
+// (0: this layer alone).  The geometry is filled in either way; a class outside the table (p.row = -1) is TNR_EINVAL.
+int plan_wgrad(const tnr_wgrad_desc *d, int group_jobs, int x3_occ, WgPlan &p) {
+    const WgRow c = wgrad_class(d, x3_occ);
+    p.row = -1;
+    for (int i = 0; i < WG_NROWS; ++i)
+        if (WG_ROWS[i] == c) p.row = i;
     const bool s2d = d->mode == TNR_CONV_4x4_S2;
-    p.a_t = d->Cout > 32 ? 2 : 1;
-    const int vch = s2d ? 4 * tnr_round_up(d->Cin, 32) : tnr_round_up(d->Cin, 32);
-    const int vblocks = vch / 32;
-    if (p.a_t == 2) {
-        p.b_t = vblocks >= 2 ? 2 : 1;
-    } else {
-        p.b_t = vblocks >= 4 ? 4 : vblocks;
-        if (vblocks == 5) p.b_t = 3;  // caller normally splits 160 = 96 + 64 itself
-    }
-    // LDS budget: two workgroups per CU (<= 80 KiB each) except the 1-workgroup regime (J >= 9, <= 160 KiB)
-    p.thg = (p.a_t == 2 || p.b_t <= 2 || (p.b_t == 4 && d->mode != TNR_CONV_4x4_S2)) ? 8 : 4;
-    const int ab = p.a_t * p.b_t;
-    p.ks = (!s2d && (ab == 1 || ab == 2)) ? 4 / ab : 1;      // WgCfg::KS
-    if (p.ks > 1) p.thg = 16;                                // each pixel group keeps >= 4 rows (J = 9: one workgroup per CU)
-    // the pre-split LDS image of TNR_MMA_BF16X3 takes 6 bytes per element: the 32 x 64 class halves its tile to stay inside 160 KB
-    if (p.ks > 1 && d->mma == TNR_MMA_BF16X3 && p.a_t == 1 && p.b_t == 2) p.thg = 8;
-    const int wpg0 = 4 / p.ks;
-    p.wps = ((p.a_t * p.b_t * (s2d ? 4 : 9) + wpg0 - 1) / wpg0 >= 9) ? 1 : 2;      // WgCfg::WAVES_PER_SIMD
-    // TNR_MMA_BF16X3, 3x3 classes: half-height tiles, two workgroups per CU (see wgrad_tile_kernel; TNR_WG_X3_OCC=1 keeps one)
-    static const int x3_occ = [] { const char *e = getenv("TNR_WG_X3_OCC"); return e ? atoi(e) : 3; }();
-    p.db = 0;
-    if (d->mma == TNR_MMA_BF16X3 && s2d && x3_occ >= 2 && p.a_t == 2 && p.b_t == 2) p.thg = 4;       // (dispatch_wgrad: two workgroups per CU)
-    if (d->mma == TNR_MMA_BF16X3 && !s2d && x3_occ >= 2 && p.wps == 1) {
-        if (p.b_t == 4) p.b_t = 2;               // 32 x 128 jobs become two 32 x 64 jobs (the 128-wide halo tile alone is 95 KB)
-        const int ab2 = p.a_t * p.b_t;
-        p.ks = (ab2 == 1 || ab2 == 2) ? 4 / ab2 : 1;
-        p.thg = ab2 == 1 ? 8 : 4;                // <= 66 KB of pre-split LDS image per tile set, >= 2 tile rows per pixel group
-        p.wps = 2;
-        // TNR_WG_X3_OCC=3 (default): the pipelined one-workgroup form with two tile sets (wgrad_tile_kernel<.., DB>), zero-padded 3x3 only
-        if (x3_occ == 3 && d->mode == TNR_CONV_3x3 && d->pad_mode == 0 && p.b_t <= 2 &&
-            (int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 30) && (int64_t)d->N * d->Ho * d->Wo * d->g.ctot < (1LL << 30)) {
-            p.wps = 1;
-            p.db = 1;
-        }
-    }
     p.cinp32 = tnr_round_up(d->Cin, 32);
-    p.KinVP = vch;
+    p.KinVP = s2d ? 4 * p.cinp32 : p.cinp32;
     p.KoutP = tnr_round_up(d->Cout, 32);
-    p.ncib = tnr_cdiv(vblocks, p.b_t);
-    p.ncob = tnr_cdiv(p.KoutP, 32 * p.a_t);
+    p.ncib = tnr_cdiv(p.KinVP / 32, c.b_t);
+    p.ncob = tnr_cdiv(p.KoutP, 32 * c.a_t);
     p.ntaps = s2d ? 4 : 9;
     p.tiles_x = tnr_cdiv(d->Wo, 16);
-    p.tiles_y = tnr_cdiv(d->Ho, p.thg);
+    p.tiles_y = tnr_cdiv(d->Ho, c.thg);
     p.tiles_total = p.tiles_x * p.tiles_y * d->N;
-    p.resident = 256 * p.wps;                    // workgroups that fit the chip at once in this regime
     const int jobs = group_jobs > 0 ? group_jobs : p.ncib * p.ncob;
-    int want = p.resident / jobs;                // one full wave of workgroups, never a straggler
+    int want = 256 * c.wps / jobs;               // one full wave of the workgroups that fit the chip at once, never a straggler
     if (want < 1) want = 1;
     int max_splits = tnr_cdiv(p.tiles_total, 4); // never fewer than 4 tiles of work per split
     if (max_splits < 1) max_splits = 1;
     p.splits = want < max_splits ? want : max_splits;
-    if (p.splits < 1) p.splits = 1;
     p.tiles_per_split = tnr_cdiv(p.tiles_total, p.splits);
     p.splits = tnr_cdiv(p.tiles_total, p.tiles_per_split);
     p.ws_floats = (int64_t)p.splits * p.ntaps * p.KoutP * p.KinVP;
     p.db_floats = (int64_t)p.splits * p.KoutP;
-    return 0;
+    TNR_REQUIRE(p.row >= 0, "wgrad: no tile class for %d -> %d channels in mode %d (mma %d, TNR_WG_X3_OCC=%d)", d->Cin, d->Cout, d->mode, d->mma, x3_occ);
+    return TNR_OK;
 }
 
-template <int MODE, int A_T, int B_T, int THG, int BF, int WPS = WgCfg<A_T, B_T, (MODE == TNR_CONV_4x4_S2 ? 4 : 9)>::WAVES_PER_SIMD, bool DB = false>
+int wgrad_x3_occ() {          // TNR_MMA_BF16X3: 1 the fp32 classes, 2 half-height tiles and two workgroups per CU, 3 also the pipelined form
+    static const int v = [] { const char *e = getenv("TNR_WG_X3_OCC"); return e ? atoi(e) : 3; }();
+    return v;
+}
+
+template <int I>
 int launch_wgrad_t(const WgK &k, int jobs, hipStream_t s) {
-    constexpr int KH = (MODE == TNR_CONV_4x4_S2) ? 2 : 3;
-    // + one halo row: the k-loop's last prefetch reads one row past the x tile (never consumed)
-    // (TNR_MMA_BF16X3: both tiles pre-split into three bf16 planes, 6 bytes per element, pixels in blocks of 4: wg_x3_off)
-    constexpr size_t lds_f32 = (size_t)(THG * 16 * 32 * A_T + (THG + KH) * (16 + KH - 1) * 32 * B_T) * sizeof(float);
-    constexpr size_t lds_x3 = (size_t)(THG * 16 * 32 * A_T + (((THG + KH - 1) * (16 + KH - 1) + 3) / 4) * 4 * 32 * B_T) * 6;
-    using Cfg = WgCfg<A_T, B_T, (MODE == TNR_CONV_4x4_S2 ? 4 : 9)>;
-    constexpr size_t lds_red = Cfg::KS > 1 ? (size_t)(Cfg::WPG * Cfg::J * 16 * 64 + Cfg::WPG * 64) * sizeof(float) : 0;   // pixel-group exchange
-    constexpr size_t lds_db = 2 * ((size_t)(THG * 16 * 32 * A_T + (THG + KH - 1) * 20 * 32 * B_T) * 6 + 3072);      // two tile sets (halo rows of 20 pixels) + their dump areas
-    constexpr size_t lds_tile = DB ? lds_db : (BF == 2 ? lds_x3 : lds_f32);
-    constexpr size_t lds = lds_tile > lds_red ? lds_tile : lds_red;
-    constexpr bool one_wg = WPS == 1;
-    if constexpr (BF == 2 && lds > 160 * 1024) {       // (a tile class plan_wgrad never picks in this mode)
-        tnr_set_error("wgrad_tile: tile class %d x %d x %d rows does not fit the LDS in TNR_MMA_BF16X3", A_T, B_T, THG);
-        return TNR_EINVAL;
-    } else {
-    // (TNR_MMA_BF16X3 classes inherited from the fp32 plan may exceed 80 KB: the LDS then limits them to one workgroup per CU)
-    static_assert(lds <= ((one_wg || BF == 2) ? 160 : 80) * 1024, "wgrad tile exceeds the LDS budget of its occupancy regime");
-    auto fn = wgrad_tile_kernel<MODE, A_T, B_T, THG, BF, WPS, DB>;
+    constexpr WgRow r = WG_ROWS[I];
+    auto fn = wgrad_tile_kernel<r.mode, r.a_t, r.b_t, r.thg, r.bf, r.wps, r.db>;
     static int cus = 0;
-    if (const int rc = tnr_kernel_setup(&cus, "wgrad_tile", {{fn, lds}})) return rc;
-    hipLaunchKernelGGL(fn, dim3(k.nsplits, jobs, 1), dim3(256), lds, s, k);
+    if (const int rc = tnr_kernel_setup(&cus, "wgrad_tile", {{fn, WG_INFO[I].lds}})) return rc;
+    hipLaunchKernelGGL(fn, dim3(k.nsplits, jobs, 1), dim3(256), WG_INFO[I].lds, s, k);
     return tnr_check_launch("wgrad_tile");
-    }
 }
 
-template <int MODE, int A_T, int B_T, int THG>
-int launch_wgrad(const WgK &k, int jobs, hipStream_t s) {
-    if (k.bf == 2) return launch_wgrad_t<MODE, A_T, B_T, THG, 2>(k, jobs, s);
-    return k.bf ? launch_wgrad_t<MODE, A_T, B_T, THG, 1>(k, jobs, s) : launch_wgrad_t<MODE, A_T, B_T, THG, 0>(k, jobs, s);
-}
-
-template <int MODE>
-int dispatch_wgrad(const WgK &k, const WgPlan &p, int jobs, hipStream_t s) {
-    constexpr int THS = (MODE == TNR_CONV_4x4_S2) ? 8 : 16;   // tile rows of the pixel-split classes (plan_wgrad: ks > 1)
-    if constexpr (MODE == TNR_CONV_3x3) {
-        if (k.bf == 2 && p.db) {                              // TNR_MMA_BF16X3: the pipelined form (plan_wgrad)
-            if (p.a_t == 2) return p.b_t == 2 ? launch_wgrad_t<MODE, 2, 2, 4, 2, 1, true>(k, jobs, s) : launch_wgrad_t<MODE, 2, 1, 4, 2, 1, true>(k, jobs, s);
-            return p.b_t == 2 ? launch_wgrad_t<MODE, 1, 2, 4, 2, 1, true>(k, jobs, s) : launch_wgrad_t<MODE, 1, 1, 8, 2, 1, true>(k, jobs, s);
-        }
-    }
-    if constexpr (MODE != TNR_CONV_4x4_S2) {
-        if (k.bf == 2 && p.wps == 2 && p.b_t <= 2) {          // TNR_MMA_BF16X3: half-height tiles, two workgroups per CU (plan_wgrad)
-            if (p.a_t == 2) return p.b_t == 2 ? launch_wgrad_t<MODE, 2, 2, 4, 2, 2>(k, jobs, s) : launch_wgrad_t<MODE, 2, 1, 4, 2, 2>(k, jobs, s);
-            return p.b_t == 2 ? launch_wgrad_t<MODE, 1, 2, 4, 2, 2>(k, jobs, s) : launch_wgrad_t<MODE, 1, 1, 8, 2, 2>(k, jobs, s);
-        }
-    }
-    if (p.a_t == 2) {
-        if constexpr (MODE == TNR_CONV_4x4_S2) {
-            // TNR_MMA_BF16X3: the 8-row tile's pre-split image is 109 KB (one workgroup per CU, nothing hides the refill); 4 rows: 58 KB, two
-            if (p.b_t == 2 && k.bf == 2 && p.thg == 4) return launch_wgrad_t<MODE, 2, 2, 4, 2, 2>(k, jobs, s);
-        }
-        if (p.b_t == 2) return launch_wgrad<MODE, 2, 2, 8>(k, jobs, s);
-        return launch_wgrad<MODE, 2, 1, THS>(k, jobs, s);
-    }
-    switch (p.b_t) {
-        case 1: return launch_wgrad<MODE, 1, 1, THS>(k, jobs, s);
-        case 2:
-            if constexpr (MODE != TNR_CONV_4x4_S2) {
-                if (p.thg == 8) return launch_wgrad_t<MODE, 1, 2, 8, 2>(k, jobs, s);          // (bf16x3 only: plan_wgrad)
-            }
-            return launch_wgrad<MODE, 1, 2, THS>(k, jobs, s);
-        case 3: return launch_wgrad<MODE, 1, 3, 4>(k, jobs, s);
-        default:
-            if constexpr (MODE != TNR_CONV_4x4_S2) {
-                if (p.thg == 8) return launch_wgrad<MODE, 1, 4, 8>(k, jobs, s);
-            }
-            return launch_wgrad<MODE, 1, 4, 4>(k, jobs, s);
-    }
+template <int... I>
+int launch_wgrad_row(int row, const WgK &k, int jobs, hipStream_t s, std::integer_sequence<int, I...>) {
+    int rc = TNR_EINVAL;
+    (void)((row == I && (rc = launch_wgrad_t<I>(k, jobs, s), true)) || ...);
+    return rc;
 }
 
 int check_wgrad_desc(const tnr_wgrad_desc *d) {
@@ -1133,39 +1081,53 @@ int check_wgrad_desc(const tnr_wgrad_desc *d) {
 extern "C" int64_t tnr_wgrad_workspace_bytes(const tnr_wgrad_desc *d) {
     if (d == nullptr) return 0;
     WgPlan p;
-    plan_wgrad(d, p, 0);   // a layer alone uses the most splits: this bound also covers any group
+    plan_wgrad(d, 0, wgrad_x3_occ(), p);   // a layer alone uses the most splits: this bound also covers any group
     return (p.ws_floats + p.db_floats) * (int64_t)sizeof(float);
+}
+
+extern "C" int tnr_wgrad_tile_class(const tnr_wgrad_desc *d, int32_t group_jobs, int32_t x3_occ, int32_t out[12]) {
+    TNR_REQUIRE(d != nullptr && out != nullptr, "wgrad_tile_class: null pointer");
+    WgPlan p;
+    if (const int rc = plan_wgrad(d, group_jobs, x3_occ < 0 ? wgrad_x3_occ() : x3_occ, p)) return rc;
+    const WgRow &r = WG_ROWS[p.row];
+    const int32_t v[12] = {r.mode, r.a_t, r.b_t, r.thg, r.bf, r.wps, r.db, WG_INFO[p.row].ks, p.splits, p.tiles_per_split, (int32_t)WG_INFO[p.row].lds, p.row};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return TNR_OK;
 }
 
 extern "C" int tnr_conv_wgrad_group(const tnr_wgrad_desc *descs, int32_t n, void *stream) {
     TNR_REQUIRE(descs != nullptr && n >= 1 && n <= TNR_WGRAD_GROUP_MAX, "wgrad_group: 1..%d layers per group", TNR_WGRAD_GROUP_MAX);
+    const tnr_wgrad_desc &d0 = descs[0];
+    const int x3_occ = wgrad_x3_occ();
     WgPlan plans[TNR_WGRAD_GROUP_MAX];
     int jobs = 0;
     for (int i = 0; i < n; ++i) {
-        const int rc = check_wgrad_desc(&descs[i]);
-        if (rc != TNR_OK) return rc;
-        plan_wgrad(&descs[i], plans[i], 0);
+        const tnr_wgrad_desc &di = descs[i];
+        if (const int rc = check_wgrad_desc(&di)) return rc;
+        TNR_REQUIRE(di.mma >= TNR_MMA_F32 && di.mma <= TNR_MMA_BF16X3, "wgrad: bad mma %d", di.mma);
+        if (const int rc = plan_wgrad(&di, 0, x3_occ, plans[i])) return rc;
         jobs += plans[i].ncib * plans[i].ncob;
-        const tnr_wgrad_desc &d0 = descs[0], &di = descs[i];
         TNR_REQUIRE(di.mode == d0.mode && di.N == d0.N && di.H == d0.H && di.W == d0.W && di.Ho == d0.Ho && di.Wo == d0.Wo,
                     "wgrad_group: layer %d does not share the pixel geometry of layer 0", i);
-        TNR_REQUIRE(plans[i].a_t == plans[0].a_t && plans[i].b_t == plans[0].b_t && plans[i].thg == plans[0].thg && plans[i].ks == plans[0].ks && plans[i].db == plans[0].db,
-                    "wgrad_group: layer %d (%d->%d channels) is not in the tile class of layer 0 (%d->%d)", i, di.Cin,
+        TNR_REQUIRE(di.pad_mode == d0.pad_mode, "wgrad_group: layer %d: one border mode per launch", i);
+        TNR_REQUIRE(di.mma == d0.mma, "wgrad_group: layer %d: one matrix-core precision per launch", i);
+        TNR_REQUIRE(plans[i].row == plans[0].row, "wgrad_group: layer %d (%d->%d channels) is not in the tile class of layer 0 (%d->%d)", i, di.Cin,
                     di.Cout, d0.Cin, d0.Cout);
     }
     TNR_REQUIRE(jobs <= 65535, "wgrad_group: too many channel blocks");
+    TNR_REQUIRE(d0.pad_mode == 0 || (d0.pad_mode == 1 && d0.mode == TNR_CONV_3x3 && d0.H >= 2 && d0.W >= 2), "wgrad: pad_mode 1 (reflection) is for TNR_CONV_3x3");
+    if (n > 1)                                   // the split count of the whole group's jobs
+        for (int i = 0; i < n; ++i) plan_wgrad(&descs[i], jobs, x3_occ, plans[i]);
+    const WgPlan &p0 = plans[0];
     WgK k;
     RedK r;
     static const int red_rpb = [] { const char *e = getenv("TNR_WGRAD_REDUCE_RPB"); return e ? atoi(e) : 8; }();      // (A/B switch: 1 = a block per row always)
-    WgPlan pg = plans[0];
-    if (n > 1) plan_wgrad(&descs[0], pg, jobs);
-    const int rpb = (red_rpb == 8 && pg.splits <= 32) ? 8 : 1;
+    const int rpb = (red_rpb == 8 && p0.splits <= 32) ? 8 : 1;
     int job_begin = 0, blk_begin = 0;
     for (int i = 0; i < n; ++i) {
         const tnr_wgrad_desc *d = &descs[i];
-        WgPlan &p = plans[i];
-        if (n > 1) plan_wgrad(d, p, jobs);
-        TNR_REQUIRE(p.splits == plans[0].splits && p.tiles_per_split == plans[0].tiles_per_split, "wgrad_group: split mismatch");
+        const WgPlan &p = plans[i];
+        TNR_REQUIRE(p.splits == p0.splits && p.tiles_per_split == p0.tiles_per_split, "wgrad_group: split mismatch");
         TNR_REQUIRE((p.ws_floats + p.db_floats) * (int64_t)sizeof(float) <= d->ws_bytes,
                     "wgrad: workspace too small (%lld < %lld)", (long long)d->ws_bytes,
                     (long long)((p.ws_floats + p.db_floats) * sizeof(float)));
@@ -1187,24 +1149,13 @@ extern "C" int tnr_conv_wgrad_group(const tnr_wgrad_desc *descs, int32_t n, void
         blk_begin += tnr_cdiv(q.nrows, rpb) + (d->db ? tnr_cdiv(d->Cout, 32) : 0);
     }
     for (int i = n; i < TNR_WGRAD_GROUP_MAX; ++i) { k.job[i] = k.job[0]; r.job[i] = r.job[0]; }
-    const tnr_wgrad_desc &d0 = descs[0];
-    const WgPlan &p0 = plans[0];
     k.N = d0.N; k.H = d0.H; k.W = d0.W; k.Ho = d0.Ho; k.Wo = d0.Wo;
     k.tiles_x = p0.tiles_x; k.tiles_y = p0.tiles_y; k.tiles_total = p0.tiles_total;
     k.tiles_per_split = p0.tiles_per_split; k.nsplits = p0.splits; k.njobs = n;
-    TNR_REQUIRE(d0.mma >= TNR_MMA_F32 && d0.mma <= TNR_MMA_BF16X3, "wgrad: bad mma %d", d0.mma);
     k.bf = d0.mma;
     k.reflect = d0.pad_mode == 1;
-    TNR_REQUIRE(d0.pad_mode == 0 || (d0.pad_mode == 1 && d0.mode == TNR_CONV_3x3 && d0.H >= 2 && d0.W >= 2), "wgrad: pad_mode 1 (reflection) is for TNR_CONV_3x3");
-    for (int i = 1; i < n; ++i) TNR_REQUIRE(descs[i].pad_mode == d0.pad_mode, "wgrad_group: layer %d: one border mode per launch", i);
-    for (int i = 1; i < n; ++i) TNR_REQUIRE(descs[i].mma == d0.mma, "wgrad_group: layer %d: one matrix-core precision per launch", i);
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-    switch (d0.mode) {
-        case TNR_CONV_3x3: rc = dispatch_wgrad<TNR_CONV_3x3>(k, p0, jobs, s); break;
-        case TNR_CONV_3x3_UP2: rc = dispatch_wgrad<TNR_CONV_3x3_UP2>(k, p0, jobs, s); break;
-        default: rc = dispatch_wgrad<TNR_CONV_4x4_S2>(k, p0, jobs, s); break;
-    }
+    const int rc = launch_wgrad_row(p0.row, k, jobs, s, std::make_integer_sequence<int, WG_NROWS>{});
     if (rc != TNR_OK) return rc;
     r.splits = p0.splits; r.ntaps = p0.ntaps; r.s2d = d0.mode == TNR_CONV_4x4_S2;
     r.kh = r.s2d ? 4 : 3; r.kw = r.kh; r.njobs = n; r.rpb = rpb;

@@ -986,6 +986,14 @@ def wgrad_group(items, mode=CONV_3x3):
     PROFILE.end("wgrad_tile", flops, t0, (sum(it["x"].C for it in items) if n > 1 else x0.C, g0.C, g0.H, mode + 100 * (n - 1)))
 
 
+def wgrad_tile_class(desc, group_jobs=0, x3_occ=-1):
+    """tnr_wgrad_tile_class of a WgradDesc (host only, no launch) -> dict of the kernel's template arguments mode / a_t / b_t / thg / bf / wps /
+    db and ks, splits, tiles_per_split, lds, row (the index in the library's table of tile classes)."""
+    out = (C.c_int32 * 12)()
+    hip.check(hip.load().tnr_wgrad_tile_class(C.byref(desc), group_jobs, x3_occ, C.byref(out)), "wgrad_tile_class")
+    return dict(zip(("mode", "a_t", "b_t", "thg", "bf", "wps", "db", "ks", "splits", "tiles_per_split", "lds", "row"), out))
+
+
 def wgrad_thin(big, small4, dw, db, flip, alpha=1.0, beta=1.0):
     """Weight gradient of a 3x3 layer with <= 3 channels on one side on the vector ALUs (tnr_wgrad_thin): flip=False
     for a 3 -> C layer (big = gradient of its output, small4 = NHWC4 input image), flip=True for a C -> 3 layer
