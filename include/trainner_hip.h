@@ -591,6 +591,26 @@ int tnr_freqsep_high_fwd(const float *x, int32_t N, int32_t C, int32_t H, int32_
 int tnr_freqsep_high_bwd(const float *g, const float *o, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const float *taps9,
                          const float *gscale, float *gx, int32_t accumulate, void *stream);
 
+/* --- DiffAugment on the discriminator inputs (dataops/diffaug.py; csrc/diffaug.hip) --------------------------------------------------
+ * out = cutout_mask . Geo(Colour(x)) of a fp32 batch N x C x H x W, C <= 4, layout 0 = NCHW-contiguous, 1 = channels-last; value and
+ * adjoint.  params: N records of 8 words on the DEVICE {float b, sat, con; int32 ty, tx, oy, ox, pad} (brightness shift, saturation
+ * and contrast factors, translation out(y, x) = in(y + ty, x + tx), cutout offsets as drawn).  geo: 9 int32 on the HOST
+ * {kind, flip, rot, offy, offx, inh, inw, color, cutout}: kind 0 identity, 1 translation, 2 zoom_in (crop inh x inw at (offy, offx),
+ * bilinear up to H x W, align_corners=False), 3 zoom_out (zero-padded frame inh x inw with the image at (-offy, -offx), bilinear
+ * down); then the horizontal flip (0 / 1) and torch.rot90's k (0, +1, -1; needs H = W); color / cutout switch those stages.
+ * tnr_diffaug_mean: ws[n][0 .. 64) = fp64 partial sums of x[n] (backward = 0), or of Geo^T(mask . g)[n] formed over the outputs
+ *   (backward = 1); only needed with color.  ws: tnr_diffaug_workspace_bytes(N).
+ * tnr_diffaug_fwd: one launch; reads ws when color is set.  tnr_diffaug_bwd: gx = Colour^T(Geo^T(mask . g)) in gather form, one
+ *   launch; reads the backward partials when color is set.  No atomics: two runs are bit-identical.  out / gx must not alias the
+ *   input. */
+int64_t tnr_diffaug_workspace_bytes(int32_t N);
+int tnr_diffaug_mean(const float *src, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const void *params,
+                     const int32_t *geo, int32_t backward, void *ws, int64_t ws_bytes, void *stream);
+int tnr_diffaug_fwd(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const void *params, const int32_t *geo,
+                    const void *ws, float *out, void *stream);
+int tnr_diffaug_bwd(const float *g_out, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const void *params,
+                    const int32_t *geo, const void *ws, float *gx, void *stream);
+
 /* --- Gram matrix of an activation (GramMatrix(out_norm='ci'), modules/loss.py:479-506: the style term of PerceptualLoss,
  * losses.py:311-326; csrc/gram.hip) -----------------------------------------------------------------------------------------------
  * x: an NHWC view [N, H, W, C], C a multiple of 64 up to 512.  mma: TNR_MMA_F32 or TNR_MMA_BF16X3 (operands split once, in the stager).

@@ -188,6 +188,10 @@ _SIGS = {
     "tnr_freqsep_low": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),
     "tnr_freqsep_high_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p]),
     "tnr_freqsep_high_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),
+    "tnr_diffaug_workspace_bytes": (c_l, [c_i]),
+    "tnr_diffaug_mean": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, C.POINTER(c_i), c_i, c_p, c_l, c_p]),
+    "tnr_diffaug_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, C.POINTER(c_i), c_p, c_p, c_p]),
+    "tnr_diffaug_bwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, C.POINTER(c_i), c_p, c_p, c_p]),
     "tnr_gram_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i]),
     "tnr_gram_fwd": (c_i, [CView, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p]),
     "tnr_gram_bwd": (c_i, [CView, c_p, c_i, c_i, c_i, c_i, c_f, c_i, CView, c_i, c_p]),

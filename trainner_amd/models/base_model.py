@@ -288,7 +288,11 @@ class BaseModel:
         train_opt = self.opt["train"]
         if train_opt["gan_type"] and train_opt["gan_weight"]:
             self.cri_gan = True
-            self.adversarial = Adversarial(train_opt=train_opt, device=self.device, diffaug=train_opt.get("diffaug"),
+            diffaug, dapolicy = train_opt.get("diffaug"), None
+            if diffaug:          # base_model.py:645-655
+                dapolicy = train_opt.get("dapolicy", "color,translation,cutout")
+                logger.info("Differential augmentations enabled")
+            self.adversarial = Adversarial(train_opt=train_opt, device=self.device, diffaug=diffaug, dapolicy=dapolicy,
                                            conditional=conditional)
             self.adversarial.dp_group = self.dp if self.dp.active else None
             self.D_update_ratio = train_opt.get("D_update_ratio", 1) or 1

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip, ops
+from ..dataops import diffaug as diffaug_ops
 from ..dataops import filters
 from . import networks
 from .modules import image_losses as IL
@@ -305,8 +306,12 @@ class Adversarial(nn.Module):
 
     def __init__(self, train_opt=None, device="cpu", diffaug=False, dapolicy="", conditional=False):
         super().__init__()
-        if diffaug or train_opt.get("gan_featmaps"):
-            raise NotImplementedError("diffaug / feature-map GAN options are not implemented by the HIP engine")
+        if train_opt.get("gan_featmaps"):
+            raise NotImplementedError("the feature-map GAN option 'gan_featmaps' is not implemented by the HIP engine")
+        self.diffaug = bool(diffaug)
+        self.dapolicy = dapolicy or ""
+        if self.diffaug:
+            diffaug_ops.parse_policy(self.dapolicy)          # an unsupported policy is refused here, not at the first step
         self.device = device
         self.conditional = bool(conditional)
         self.gan_type = train_opt["gan_type"]
@@ -337,6 +342,13 @@ class Adversarial(nn.Module):
             fake = fsfilter(fake if stage == "generator" else fake.detach())
             if isinstance(real, torch.Tensor):
                 real = fsfilter(real)
+        if self.diffaug:
+            # losses.py:578-582: after the frequency separation and before the conditional concatenation (the condition is not
+            # augmented); fake and real are separate calls with their own draws, in both stages.  The results are new storage on
+            # every call, so netD's forward memo simply misses on them
+            fake = diffaug_ops.DiffAugment(fake if stage == "generator" else fake.detach(), policy=self.dapolicy)
+            if isinstance(real, torch.Tensor):
+                real = diffaug_ops.DiffAugment(real, policy=self.dapolicy)
         if self.conditional:
             # like the reference's dispatch (losses.py:590-604) the second positional argument is the condition in the
             # generator stage (pix2pix_model.py:152-154 passes it by keyword)

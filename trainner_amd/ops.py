@@ -1361,6 +1361,33 @@ def freqsep_high_bwd(g, o, layout, taps9, gx, gscale=None, accumulate=False):
                                               gx.data_ptr(), int(accumulate), hip.stream()), "freqsep_high_bwd")
 
 
+# DiffAugment (csrc/diffaug.hip): out = cutout_mask . Geo(Colour(x)).  params: fp32 [N, 8] on the device (the int fields written through
+# an int32 view), geo: the 9 host integers {kind, flip, rot, offy, offx, inh, inw, color, cutout} (dataops/diffaug.py builds both).
+def _diffaug_ws(x):
+    return WS.get("diffaug@%x" % hip.stream(), hip.load().tnr_diffaug_workspace_bytes(x.shape[0]), x.device)
+
+
+def diffaug_mean(src, layout, params, geo, backward=False):
+    """-> the workspace with the fp64 partial sums of src[n] (forward) or of the pulled-back gradient (backward); one launch."""
+    N, Ch, H, W = src.shape
+    ws = _diffaug_ws(src)
+    hip.check(hip.load().tnr_diffaug_mean(src.data_ptr(), N, Ch, H, W, layout, params.data_ptr(), (C.c_int32 * 9)(*geo), int(backward),
+                                          ws.data_ptr(), ws.numel() * 8, hip.stream()), "diffaug_mean")
+    return ws
+
+
+def diffaug_fwd(x, layout, params, geo, ws, out):
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_diffaug_fwd(x.data_ptr(), N, Ch, H, W, layout, params.data_ptr(), (C.c_int32 * 9)(*geo), hip.ptr(ws),
+                                         out.data_ptr(), hip.stream()), "diffaug_fwd")
+
+
+def diffaug_bwd(g, layout, params, geo, ws, gx):
+    N, Ch, H, W = g.shape
+    hip.check(hip.load().tnr_diffaug_bwd(g.data_ptr(), N, Ch, H, W, layout, params.data_ptr(), (C.c_int32 * 9)(*geo), hip.ptr(ws),
+                                         gx.data_ptr(), hip.stream()), "diffaug_bwd")
+
+
 # Gram matrix of an activation view and its gradient (csrc/gram.hip).  Always on the fp32 activations and in the fp32 arithmetic of
 # TNR_MMA (FP32_MMA), also under `use_amp`: stricter than the reference, whose autocast runs the bmm in half precision.
 def gram_fwd(x, scale, G):
