@@ -611,6 +611,23 @@ int tnr_diffaug_fwd(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, 
 int tnr_diffaug_bwd(const float *g_out, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, const void *params,
                     const int32_t *geo, const void *ws, float *gx, void *stream);
 
+/* --- Batch augmentations of the (target, input) pair (dataops/batchaug.py; csrc/batchaug.hip) -----------------------------------------
+ * fp32 batches N x C x H x W, C <= 4, layout 0 = NCHW-contiguous, 1 = channels-last.  No op moves a pixel.
+ * tnr_batchaug_mix: one output from x, an optional second source x2 of the same shape (read at image r[n]; r: N int32 on the DEVICE,
+ *   null = the identity) and col (N x 3 floats on the DEVICE).  prm: 10 int32 on the HOST {inside, outside, y0, x0, bh, bw, p0 .. p3}:
+ *   the box of bh x bw pixels at (y0, x0) (the same in every image; empty when bh or bw is 0) and the code of the region inside and
+ *   outside it: 0 SELF x[n, p_c] (bitwise copy), 1 PARTNER x2[r[n], c] (bitwise copy), 2 LERP_PARTNER fl(a x[n, c]) + fl(b x2[r[n], c]),
+ *   3 LERP_COLOUR fl(a x[n, c]) + fl(b col[n, c]) (C = 3 only).  A channel permutation other than the identity goes with SELF
+ *   regions only.  A source is read only where a region needs it.  out must not alias a source.
+ * tnr_batchaug_mask: out = x * (float)mask[n, y / s, x / s], mask uint8 N x (H / s) x (W / s) on the DEVICE, s >= 1 dividing H and W;
+ *   a real product; its own adjoint; out may be x.
+ * 16-byte accesses when the row length (W, or W * C channels-last) is a multiple of 4 and the pointers are 16-byte aligned, scalar
+ * ones otherwise (and for a channels-last channel permutation).  One launch each, no atomics, no workspace. */
+int tnr_batchaug_mix(const float *x, const float *x2, const int32_t *r, const float *col, int32_t N, int32_t C, int32_t H, int32_t W,
+                     int32_t layout, const int32_t *prm, float a, float b, float *out, void *stream);
+int tnr_batchaug_mask(const float *x, const uint8_t *mask, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t s,
+                      float *out, void *stream);
+
 /* --- Gram matrix of an activation (GramMatrix(out_norm='ci'), modules/loss.py:479-506: the style term of PerceptualLoss,
  * losses.py:311-326; csrc/gram.hip) -----------------------------------------------------------------------------------------------
  * x: an NHWC view [N, H, W, C], C a multiple of 64 up to 512.  mma: TNR_MMA_F32 or TNR_MMA_BF16X3 (operands split once, in the stager).

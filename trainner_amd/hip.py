@@ -192,6 +192,8 @@ _SIGS = {
     "tnr_diffaug_mean": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, C.POINTER(c_i), c_i, c_p, c_l, c_p]),
     "tnr_diffaug_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, C.POINTER(c_i), c_p, c_p, c_p]),
     "tnr_diffaug_bwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, C.POINTER(c_i), c_p, c_p, c_p]),
+    "tnr_batchaug_mix": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_i), c_f, c_f, c_p, c_p]),
+    "tnr_batchaug_mask": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "tnr_gram_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i]),
     "tnr_gram_fwd": (c_i, [CView, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p]),
     "tnr_gram_bwd": (c_i, [CView, c_p, c_i, c_i, c_i, c_i, c_f, c_i, CView, c_i, c_p]),

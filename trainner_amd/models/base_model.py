@@ -270,8 +270,19 @@ class BaseModel:
         self._reject(self.opt.get("use_atg"), "AdaTarget (use_atg)")
 
     def setup_batchaug(self):
-        self.mixup = None
-        self._reject(self.opt["train"].get("mixup"), "batch augmentation (mixup)")
+        """base_model.py:618-627: `mixup` switches the batch augmentations on (dataops/batchaug.py).  Every data-parallel rank augments
+        its own shard with its own draws."""
+        train_opt = self.opt["train"]
+        self.mixup = train_opt.get("mixup")
+        if self.mixup:
+            from ..dataops.batchaug import BatchAugment
+            self.batchaugment = BatchAugment(train_opt)
+            scale = self.opt.get("scale") or 1
+            if "cutblur" in self.batchaugment.mixopts and scale != 1:
+                raise NotImplementedError(
+                    "batch augmentation 'cutblur' with scale {} is not implemented by the HIP engine: the reference up-samples the input "
+                    "to the target's size, feeds that HR-sized image to the x{} generator and fails at the first loss".format(scale, scale))
+            logger.info("Batch augmentations enabled")
 
     def setup_fs(self):
         """base_model.py:629-639: `fs` switches frequency separation on; `lpf_type` / `hpf_type` (default average) pick the filters."""

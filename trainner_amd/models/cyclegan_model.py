@@ -145,7 +145,12 @@ class CycleGANModel(BaseModel):
     @training_step
     def optimize_parameters(self, step):
         eff_step = step / self.accumulations
+        if self.mixup:          # cyclegan_model.py:321-332: rec_A / rec_B come from the unmasked fakes
+            self.real_B, self.real_A = self.batchaugment(self.real_B, self.real_A)
         self.forward()
+        if self.mixup:
+            self.fake_B, self.real_B = self.batchaugment.apply_mask(self.fake_B, self.real_B)
+            self.fake_A, self.real_A = self.batchaugment.apply_mask(self.fake_A, self.real_A)
         if self.cri_gan:
             self.requires_grad(self.netD_A, flag=False, net_type="D")
             self.requires_grad(self.netD_B, flag=False, net_type="D")

@@ -84,7 +84,11 @@ class Pix2PixModel(BaseModel):
     @training_step
     def optimize_parameters(self, step):
         eff_step = step / self.accumulations
+        if self.mixup:          # pix2pix_model.py:191-201
+            self.real_B, self.real_A = self.batchaugment(self.real_B, self.real_A)
         self.forward()
+        if self.mixup:
+            self.fake_B, self.real_B = self.batchaugment.apply_mask(self.fake_B, self.real_B)
         if self.cri_gan:
             self.requires_grad(self.netD, flag=True)
             if isinstance(self.feature_loc, int):

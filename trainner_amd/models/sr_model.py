@@ -128,7 +128,11 @@ class SRModel(BaseModel):
         eff_step = step / self.accumulations
         if self.cri_gan:
             self.requires_grad(self.netD, flag=False, net_type="D")
+        if self.mixup:          # sr_model.py:218-228: the pair before the forward, the cutout mask after it (var_ref is not touched)
+            self.real_H, self.var_L = self.batchaugment(self.real_H, self.var_L)
         self.forward()
+        if self.mixup:
+            self.fake_H, self.real_H = self.batchaugment.apply_mask(self.fake_H, self.real_H)
         if (self.cri_gan is not True) or (eff_step % self.D_update_ratio == 0 and eff_step > self.D_init_iters):
             self.backward_G()
             self.optimizer_step(step, self.optimizer_G, "G")

@@ -1388,6 +1388,21 @@ def diffaug_bwd(g, layout, params, geo, ws, gx):
                                          gx.data_ptr(), hip.stream()), "diffaug_bwd")
 
 
+# Batch augmentations (csrc/batchaug.hip).  prm: the 10 host integers {inside, outside, y0, x0, bh, bw, p0 .. p3}
+# (dataops/batchaug.py builds them); x2 / r / col may be None where no region needs them.
+def batchaug_mix(x, layout, prm, a, b, out, x2=None, r=None, col=None):
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_batchaug_mix(x.data_ptr(), hip.ptr(x2), hip.ptr(r), hip.ptr(col), N, Ch, H, W, layout,
+                                          (C.c_int32 * 10)(*prm), float(a), float(b), out.data_ptr(), hip.stream()), "batchaug_mix")
+
+
+def batchaug_mask(x, layout, mask, s, out):
+    """out = x * mask[n, y // s, x // s]; mask: uint8 N x (H / s) x (W / s), contiguous, on x's device."""
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_batchaug_mask(x.data_ptr(), mask.data_ptr(), N, Ch, H, W, layout, int(s), out.data_ptr(), hip.stream()),
+              "batchaug_mask")
+
+
 # Gram matrix of an activation view and its gradient (csrc/gram.hip).  Always on the fp32 activations and in the fp32 arithmetic of
 # TNR_MMA (FP32_MMA), also under `use_amp`: stricter than the reference, whose autocast runs the bmm in half precision.
 def gram_fwd(x, scale, G):
