@@ -575,6 +575,36 @@ int tnr_pointwise_loss_fwd(const float *a, const float *b, int64_t n, int32_t cr
 int tnr_pointwise_loss_bwd(const float *a, const float *b, int64_t n, int32_t crit, double scale, const float *gscale, float *ga,
                            int32_t accumulate, void *stream);
 
+/* tnr_overflow_loss_*: OFLoss (modules/loss.py:527-542) with legit_range [0, 1] over n fp32 elements of any dense layout:
+ *   loss[0] = scale * sum log(|x - clamp(x, 0, 1)| + 1) (ws: tnr_reduce_workspace_bytes); bwd writes (or adds, `accumulate`)
+ *   gx = scale * gscale[0] * sign(d) / (|d| + 1) for d = x - clamp(x, 0, 1), which is 0 on the closed interval. */
+int tnr_overflow_loss_fwd(const float *x, int64_t n, double scale, float *loss, void *ws, void *stream);
+int tnr_overflow_loss_bwd(const float *x, int64_t n, double scale, const float *gscale, float *gx, int32_t accumulate, void *stream);
+
+/* --- spatial profile losses (modules/loss.py SPLoss :741-757, GPLoss :616-649, CPLoss :652-707; csrc/spl_loss.hip) ------------------
+ * SPLoss(D, E) = -(sum over every column of every (n, k) plane of cos(column of D, column of E) + the same over rows) / (H N), each
+ * cosine as F.normalize forms it: D / max(|D|, 1e-12) . E / max(|E|, 1e-12).  x (carries the gradient) and y: fp32 N x C x H x W,
+ * layout 0 = NCHW-contiguous, 1 = channels-last.  `mask` selects the families of derived planes the traces run on:
+ *   TNR_SPL_RGB   the channels themselves                                  (C <= 4)
+ *   TNR_SPL_YUV   rgb_to_yuv, BT.601: y = .299 r + .587 g + .114 b, u = .493 (b - y) + .5, v = .877 (r - y) + .5   (C == 3)
+ *   TNR_SPL_DIMG  dx = right - image (0 in the last column) and dy = bottom - image (0 in the last row), one trace each   (C <= 4)
+ *   TNR_SPL_DYUV  the same differences of the YUV image                    (C == 3)
+ * CPLoss = RGB | YUV | DYUV, GPLoss = DIMG.  `denorm` != 0 maps both images by clamp((v + 1) / 2, 0, 1) on load (derivative 0.5 on
+ * the closed interval).
+ * tnr_spl_loss_fwd: loss[f] = family f's value (0 when not selected) for f = 0 .. 3 in the order above, loss[4] = their sum; coef
+ *   (tnr_spl_coef_bytes; kept for the backward) receives per line of every derived plane alpha = 1 / (nx ny) and
+ *   beta = Sxy / (nx^3 ny), nx = max(sqrt(Sxx), 1e-12); where sqrt(Sxx) < 1e-12 beta = 0 (the clamp passes no gradient to the norm).
+ *   ws: tnr_spl_workspace_bytes.  Three launches; fp64 partials in a fixed order, no atomics.
+ * tnr_spl_loss_bwd: gx (x's shape and layout, never x or y) = or += (`accumulate`) sum over the families of gscale[f] * d loss[f] / dx;
+ *   gscale: 4 floats on the device, NULL = all 1.  Nothing flows through the zeroed last column of dx / last row of dy. */
+enum { TNR_SPL_RGB = 1, TNR_SPL_YUV = 2, TNR_SPL_DIMG = 4, TNR_SPL_DYUV = 8 };
+int64_t tnr_spl_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t mask);
+int64_t tnr_spl_coef_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t mask);
+int tnr_spl_loss_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t mask,
+                     int32_t denorm, float *loss, float *coef, void *ws, int64_t ws_bytes, void *stream);
+int tnr_spl_loss_bwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t mask,
+                     int32_t denorm, const float *coef, const float *gscale, float *gx, int32_t accumulate, void *stream);
+
 /* --- frequency separation (dataops/filters.py FilterLow :643-671, FilterHigh :674-717; csrc/freqsep.hip) ---------------------------
  * L = the zero-padded 9 x 9 low-pass of a fp32 batch N x C x H x W (layout 0 = NCHW-contiguous, 1 = channels-last), evaluated
  * separably from the 9 taps `taps9` on the HOST (2-D taps = their outer product; average: 1/9 each; Gaussian: sigma 1.5, normalised).

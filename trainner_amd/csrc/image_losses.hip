@@ -10,6 +10,7 @@
 //   fd_fwd_kernel      finite differences (dataops/filters.py:722-777, quirks included) of x and of y, rho of their difference, partial sum
 //   fd_bwd_kernel      gathers every pixel's gradient from the responses of its 3 x 3 neighbourhood, recomputed from x and y in LDS
 //   point_*_kernel     rho(a - b) over a flat dense range (pixel_criterion other than l1)
+//   overflow_*_kernel  log(|x - clamp(x, 0, 1)| + 1) over a flat dense range (OFLoss :527-542)
 //   sum_kernel         the blocks' partials in a fixed order -> loss = scale * sum
 //
 // All reductions are fixed-order (one fp64 slot per block, then one block): two runs are bit-identical.  No float atomics.
@@ -301,6 +302,55 @@ __global__ __launch_bounds__(256) void point_bwd_kernel(const float *__restrict_
     }
 }
 
+// OFLoss: log(|x - clamp(x, 0, 1)| + 1); its derivative sign(d) / (|d| + 1) is 0 on the closed interval, where d is exactly 0
+__device__ __forceinline__ float overflow_of(float v) { return v - fminf(fmaxf(v, 0.f), 1.f); }
+
+__global__ __launch_bounds__(256) void overflow_fwd_kernel(const float *__restrict__ x, int64_t n, int vec, double *__restrict__ partial) {
+    __shared__ double sh[256];
+    double acc = 0;
+    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    int64_t tail = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = t0; i < n4; i += step) {
+            const f32x4 v = ((const f32x4 *)x)[i];
+            const float r = (log1pf(fabsf(overflow_of(v.x))) + log1pf(fabsf(overflow_of(v.y)))) +
+                            (log1pf(fabsf(overflow_of(v.z))) + log1pf(fabsf(overflow_of(v.w))));
+            acc += (double)r;
+        }
+        tail = n4 << 2;
+    }
+    for (int64_t i = tail + t0; i < n; i += step) acc += (double)log1pf(fabsf(overflow_of(x[i])));
+    acc = tnr_block_sum256(acc, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(256) void overflow_bwd_kernel(const float *__restrict__ x, int64_t n, int vec, float scale,
+                                                           const float *__restrict__ gscale, float *__restrict__ gx, int accumulate) {
+    const float mul = scale * (gscale ? *gscale : 1.f);
+    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    const auto d = [mul](float v) {
+        const float e = overflow_of(v);
+        return mul * sgn(e) / (fabsf(e) + 1.f);
+    };
+    int64_t tail = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = t0; i < n4; i += step) {
+            const f32x4 v = ((const f32x4 *)x)[i];
+            f32x4 r;
+            r.x = d(v.x); r.y = d(v.y); r.z = d(v.z); r.w = d(v.w);
+            if (accumulate) r += ((const f32x4 *)gx)[i];
+            ((f32x4 *)gx)[i] = r;
+        }
+        tail = n4 << 2;
+    }
+    for (int64_t i = tail + t0; i < n; i += step) {
+        const float r = d(x[i]);
+        gx[i] = accumulate ? gx[i] + r : r;
+    }
+}
+
 int check_crit(const char *what, int crit) {
     TNR_REQUIRE(crit >= CRIT_L1 && crit <= CRIT_CLIPL1, "%s: unknown criterion %d", what, crit);
     return TNR_OK;
@@ -405,4 +455,26 @@ extern "C" int tnr_pointwise_loss_bwd(const float *a, const float *b, int64_t n,
     hipLaunchKernelGGL(point_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a, b, n, vec, (int)crit, (float)scale, gscale, ga,
                        (int)accumulate);
     return tnr_check_launch("pointwise_loss_bwd");
+}
+
+extern "C" int tnr_overflow_loss_fwd(const float *x, int64_t n, double scale, float *loss, void *ws, void *stream) {
+    TNR_REQUIRE(x && loss && ws && n > 0, "overflow_loss_fwd: bad arguments");
+    const int vec = aligned16(x);
+    int64_t nb = tnr_cdiv64(vec ? tnr_cdiv64(n, 4) : n, 256);
+    if (nb > PT_BLOCKS) nb = PT_BLOCKS;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(overflow_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, s, x, n, vec, (double *)ws);
+    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)ws, nb, scale, loss);
+    return tnr_check_launch("overflow_loss_fwd");
+}
+
+extern "C" int tnr_overflow_loss_bwd(const float *x, int64_t n, double scale, const float *gscale, float *gx, int32_t accumulate,
+                                     void *stream) {
+    TNR_REQUIRE(x && gx && x != gx && n > 0, "overflow_loss_bwd: bad arguments");
+    const int vec = aligned16(x) && aligned16(gx);
+    int64_t nb = tnr_cdiv64(vec ? tnr_cdiv64(n, 4) : n, 256);
+    if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(overflow_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, n, vec, (float)scale, gscale, gx,
+                       (int)accumulate);
+    return tnr_check_launch("overflow_loss_bwd");
 }

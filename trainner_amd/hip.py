@@ -185,6 +185,12 @@ _SIGS = {
     "tnr_fd_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, C.c_double, c_p, c_p, c_i, c_p]),
     "tnr_pointwise_loss_fwd": (c_i, [c_p, c_p, c_l, c_i, C.c_double, c_p, c_p, c_p]),
     "tnr_pointwise_loss_bwd": (c_i, [c_p, c_p, c_l, c_i, C.c_double, c_p, c_p, c_i, c_p]),
+    "tnr_overflow_loss_fwd": (c_i, [c_p, c_l, C.c_double, c_p, c_p, c_p]),
+    "tnr_overflow_loss_bwd": (c_i, [c_p, c_l, C.c_double, c_p, c_p, c_i, c_p]),
+    "tnr_spl_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i]),
+    "tnr_spl_coef_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i]),
+    "tnr_spl_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_l, c_p]),
+    "tnr_spl_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p]),
     "tnr_freqsep_low": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),
     "tnr_freqsep_high_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p]),
     "tnr_freqsep_high_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), c_p, c_p, c_i, c_p]),

@@ -9,7 +9,8 @@ loss over any dictionary of layers (`perceptual_opt.perceptual_layers`) and the 
 (`ssim_type` / `ssim_weight`, losses.py:798-802) and the recipe's edge / smoothness terms
 (train_sr.yml:114-120): the difference-only pixel criteria l2, cb, elastic and clipl1, HFEN (`hfen_criterion` /
 `hfen_weight`), total variation (`tv_type` / `tv_norm` / `tv_weight`) and the image-gradient loss of the precise list
-(`grad_type` / `grad_weight`).  With frequency separation (`fs`, base_model.setup_fs) `GeneratorLoss` hands the low-passed images to
+(`grad_type` / `grad_weight`), and the first two experimental terms (train_sr.yml "Experimental losses"): the spatial profile losses
+(`spl_type: spl | cpl | gpl` / `spl_weight`) and the overflow loss (`of_type: overflow` / `of_weight`).  With frequency separation (`fs`, base_model.setup_fs) `GeneratorLoss` hands the low-passed images to
 the colour / content terms and `Adversarial` shows the discriminator the high-pass residual (dataops/filters.py).  Anything else
 raises NotImplementedError (no silent fallback to eager PyTorch).
 """
@@ -21,6 +22,7 @@ from ..dataops import diffaug as diffaug_ops
 from ..dataops import filters
 from . import networks
 from .modules import image_losses as IL
+from .modules import spl as SPL
 from .modules._dense import dense_layout, gscale
 from .modules.ssim import MS_SSIM, SSIM
 
@@ -193,6 +195,13 @@ def get_loss_fn(loss_type=None, weight=0, recurrent=False, reduction="mean", net
         if len(parts) != 3:
             raise NotImplementedError("Loss type [{}] is not implemented by the HIP engine".format(loss_type))
         loss_function = IL.GradientLoss(loss_f=IL.criterion(parts[2]), gradientdir=parts[1])
+    elif loss_type in ("gpl", "cpl"):
+        # losses.py:100-110: both read datasets.train.znorm
+        z_norm = (((opt or {}).get("datasets") or {}).get("train") or {}).get("znorm", False)
+        loss_function = (SPL.GPLoss(spl_denorm=z_norm) if loss_type == "gpl" else
+                         SPL.CPLoss(rgb=True, yuv=True, yuvgrad=True, spl_denorm=z_norm, yuv_denorm=z_norm))
+    elif loss_type == "overflow":
+        loss_function = SPL.OFLoss()            # losses.py:140-141
     elif loss_type is not None and loss_type.find("tv") >= 0:
         parts = loss_type.split("-")            # tv-l1 | tv-l2 | dtv-l1 | dtv-l2 (losses.py:111-116)
         if len(parts) != 2 or parts[0] not in ("tv", "dtv") or parts[1] not in ("l1", "l2"):
@@ -403,10 +412,10 @@ def ops_mean(pred):
 
 
 class GeneratorLoss(nn.Module):
-    """Weighted list of generator losses (losses.py:607-962): pixel, hfen, tv, contextual, feature, then the precise list grad, ssim;
-    same order and names."""
+    """Weighted list of generator losses (losses.py:607-962): pixel, hfen, tv, contextual, feature, cpl, gpl, overflow, then the
+    precise list grad, ssim; same order and names."""
 
-    _UNSUPPORTED = ("color_weight", "avg_weight", "ms_weight", "spl_weight", "of_weight",
+    _UNSUPPORTED = ("color_weight", "avg_weight", "ms_weight",
                     "lpips_weight", "fft_weight",
                     "fdpl_weight", "range_weight")
 
@@ -444,6 +453,16 @@ class GeneratorLoss(nn.Module):
             self.cri_fea = True
         else:
             self.cri_fea = None
+        # losses.py:642-659,761-769: spl_type spl -> cpl and gpl, each with spl_weight; any other spl_type builds nothing
+        spl_weight = train_opt.get("spl_weight", 0) or 0
+        spl_type = train_opt.get("spl_type", None)
+        for name in ("cpl", "gpl"):
+            if spl_weight > 0 and spl_type in ("spl", name):
+                self.loss_list.append(get_loss_fn(name, spl_weight, opt=opt, device=device))
+        of_weight = train_opt.get("of_weight", 0) or 0
+        of_type = train_opt.get("of_type", None)
+        if of_weight > 0 and of_type:
+            self.loss_list.append(get_loss_fn(of_type, of_weight, device=device))
         # the "precise" terms (losses.py:780-816), evaluated by the models after the GAN term and always in fp32
         self.precise_loss_list = []
         grad_weight = train_opt.get("grad_weight", 0) or 0
@@ -489,7 +508,8 @@ class GeneratorLoss(nn.Module):
     def _log(self, log_dict, name, effective):
         # under data parallelism the logged value is the global-batch mean, as the reference computes it on the gathered batch.
         # The gradient needs no extra collective: every term here but the sum-reduced HFEN ones (see _effective) is a batch mean
-        # over equal shards, so averaging the ranks' gradients makes it the global-batch gradient
+        # over equal shards, so averaging the ranks' gradients makes it the global-batch gradient.  cpl, gpl and overflow are such
+        # means too (SPLoss divides its per-image line cosines by the batch size): no collective, no world-size factor
         log_dict[name] = self.dp_group.mean_scalar(effective) if self.dp_group is not None else effective.detach()
 
     @staticmethod
@@ -511,9 +531,9 @@ class GeneratorLoss(nn.Module):
         results = []
         for l in loss_list:
             name, f = l["name"], l["function"]
-            if "tv" in name:
+            if "tv" in name or "overflow" in name:
                 effective = self._effective(l, f(lp("sr", sr)))                     # fake_H alone
-            elif "pix" in name or "hfen" in name:
+            elif "pix" in name or "hfen" in name or "cpl" in name or "gpl" in name:
                 effective = self._effective(l, f(lp("sr", sr), lp("hr", hr)))
             elif "ssim" in name:
                 effective = l["weight"] * (1 - f(lp("sr", sr), lp("hr", hr)))
@@ -564,11 +584,11 @@ class GeneratorLoss(nn.Module):
         for l in self.loss_list:
             if "fea-vgg" in l["name"]:
                 effective = self._fea_effective(l, *l["function"](sr, hr))
-            elif "tv" in l["name"]:
+            elif "tv" in l["name"] or "overflow" in l["name"]:
                 effective = self._effective(l, l["function"](self._fp32(sr)))              # fake_H alone
             elif l["name"] == "contextual":
                 effective = l["weight"] * self._contextual(l["function"], sr, hr)
-            elif isinstance(l["function"], (IL.HFENLoss, IL._Criterion)):
+            elif l["name"] in ("cpl", "gpl") or isinstance(l["function"], (IL.HFENLoss, IL._Criterion)):
                 effective = self._effective(l, l["function"](self._fp32(sr), self._fp32(hr)))   # fp32 kernels with or without AMP
             else:
                 effective = l["weight"] * l["function"](sr, hr)

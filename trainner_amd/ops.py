@@ -1339,6 +1339,43 @@ def pointwise_loss_bwd(a, b, crit, scale, gscale, ga, accumulate=False):
                                                 int(accumulate), hip.stream()), "pointwise_loss_bwd")
 
 
+def overflow_loss_fwd(x, scale, loss):
+    """loss (1 float) = scale * sum log(|x - clamp(x, 0, 1)| + 1) over a dense x of any rank."""
+    hip.check(hip.load().tnr_overflow_loss_fwd(x.data_ptr(), x.numel(), float(scale), loss.data_ptr(), _reduce_ws(x.device).data_ptr(),
+                                               hip.stream()), "overflow_loss_fwd")
+
+
+def overflow_loss_bwd(x, scale, gscale, gx, accumulate=False):
+    hip.check(hip.load().tnr_overflow_loss_bwd(x.data_ptr(), x.numel(), float(scale), hip.ptr(gscale), gx.data_ptr(), int(accumulate),
+                                               hip.stream()), "overflow_loss_bwd")
+
+
+# Spatial profile losses (csrc/spl_loss.hip).  mask: the families of derived planes the SPLoss traces run on; loss: 5 floats, one per
+# family in the order of the bits and their sum; coef (spl_coef): the per-line backward coefficients the forward leaves.
+SPL_RGB, SPL_YUV, SPL_DIMG, SPL_DYUV = 1, 2, 4, 8
+SPL_CPL, SPL_GPL = SPL_RGB | SPL_YUV | SPL_DYUV, SPL_DIMG
+
+
+def spl_coef(x, mask):
+    N, Ch, H, W = x.shape
+    return torch.empty(hip.load().tnr_spl_coef_bytes(N, Ch, H, W, mask) // 4, dtype=torch.float32, device=x.device)
+
+
+def spl_loss_fwd(x, y, layout, mask, denorm, loss, coef):
+    lib = hip.load()
+    N, Ch, H, W = x.shape
+    ws = WS.get("spl@%x" % hip.stream(), lib.tnr_spl_workspace_bytes(N, Ch, H, W, mask), x.device)
+    hip.check(lib.tnr_spl_loss_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, mask, int(bool(denorm)), loss.data_ptr(), coef.data_ptr(),
+                                   ws.data_ptr(), ws.numel() * 8, hip.stream()), "spl_loss_fwd")
+
+
+def spl_loss_bwd(x, y, layout, mask, denorm, coef, gscale, gx, accumulate=False):
+    """gscale: 4 floats on the device, one per family (None = all 1)."""
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_spl_loss_bwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, mask, int(bool(denorm)), coef.data_ptr(),
+                                          hip.ptr(gscale), gx.data_ptr(), int(accumulate), hip.stream()), "spl_loss_bwd")
+
+
 # Frequency separation: the zero-padded 9 x 9 low-pass L from its 9 separable taps and the separator high-pass
 # clamp((x - L x + 1) / 2, 0, 1); one launch each.
 def freqsep_low(x, layout, taps9, out, gscale=None, accumulate=False):
