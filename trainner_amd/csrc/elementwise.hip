@@ -443,7 +443,7 @@ extern "C" int tnr_maxpool2_fwd(tnr_view x, tnr_view y, int32_t N, int32_t H, in
 
 extern "C" int tnr_maxpool2_bwd(tnr_view gy, tnr_view x, tnr_view gx, int32_t N, int32_t H, int32_t W, int32_t C,
                                 void *stream) {
-    TNR_REQUIRE(view_ok(gy) && view_ok(x) && view_ok(gx) && (C % 4) == 0, "maxpool2_bwd: bad arguments");
+    TNR_REQUIRE(view_ok(gy) && view_ok(x) && view_ok(gx) && (C % 4) == 0 && (H % 2) == 0 && (W % 2) == 0, "maxpool2_bwd: bad arguments");
     const int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total)), dim3(EW_BLOCK), 0, (hipStream_t)stream, gy.ptr, gy.ctot,
                        gy.coff, x.ptr, x.ctot, x.coff, gx.ptr, gx.ctot, gx.coff, N, H, W, C);

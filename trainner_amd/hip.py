@@ -215,8 +215,8 @@ _SIGS = {
     "tnr_cx_norm_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, CView, c_p]),
     "tnr_sumsq": (c_i, [c_p, c_l, c_p, c_p, c_p]),
     "tnr_clip_by_norm": (c_i, [c_p, c_l, c_p, c_f, c_p]),
-    "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),
-    "tnr_adam_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
+    "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, C.c_double, C.c_double, c_f, c_f, c_f, c_p]),
+    "tnr_adam_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, C.c_double, C.c_double, c_f, c_f, c_f, c_p, c_p]),
     "tnr_set_fault_word": (c_i, [c_p]),
 }
 
