@@ -146,8 +146,11 @@ __global__ void __launch_bounds__(256) wgrad_thin_reduce_kernel(const WThinRedK 
         }
     } else if (i < nmain + a.Cs && a.flip && a.db != nullptr) {
         const int cs = i - nmain;
-        float sum = 0.f;
-        for (int g = 0; g < a.grid; ++g) sum += a.ws_small[(size_t)g * 4 + cs];
+        // (up to WT_GRID partials in ONE chain: summed in fp32 it was 6 x the error of a pairwise fp32 sum at 513 workgroups; fp64 costs
+        //  three threads a few hundred adds)
+        double sum64 = 0.0;
+        for (int g = 0; g < a.grid; ++g) sum64 += (double)a.ws_small[(size_t)g * 4 + cs];
+        const float sum = (float)sum64;
         a.db[cs] = (a.beta != 0.f ? a.beta * a.db[cs] : 0.f) + a.alpha * sum;
     }
 }

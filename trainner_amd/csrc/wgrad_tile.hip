@@ -536,8 +536,10 @@ wgrad_tile_kernel(const WgK ga) {
                     if constexpr (r + 1 == ROWS && jp + 1 == NP) __syncthreads();
                     if constexpr (jp == 0) {
                         if (want_bias) {           // hi + mid + lo reconstructs the fp32 value exactly
+                            float brow = 0.f;      // (a tile row's 8 values first: see the fp32 k-loop)
 #pragma unroll
-                            for (int kk = 0; kk < 8; ++kk) bsum += ((float)fa[0][kk] + (float)fa[1][kk]) + (float)fa[2][kk];
+                            for (int kk = 0; kk < 8; ++kk) brow += ((float)fa[0][kk] + (float)fa[1][kk]) + (float)fa[2][kk];
+                            bsum += brow;
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -662,8 +664,10 @@ wgrad_tile_kernel(const WgK ga) {
                         frag(ga_ptr, ca, GA_RD);
                         if (NSET == 2) read_pair(0, 0);
                         if (want_bias) {           // hi + mid + lo reconstructs the fp32 value exactly
+                            float brow = 0.f;      // (a tile row's 8 values first: see the fp32 k-loop)
     #pragma unroll
-                            for (int kk = 0; kk < 8; ++kk) bsum += ((float)ca[0][kk] + (float)ca[1][kk]) + (float)ca[2][kk];
+                            for (int kk = 0; kk < 8; ++kk) brow += ((float)ca[0][kk] + (float)ca[1][kk]) + (float)ca[2][kk];
+                            bsum += brow;
                         }
     #pragma unroll
                         for (int jp = 0; jp < NP; ++jp) {
@@ -695,13 +699,15 @@ wgrad_tile_kernel(const WgK ga) {
                         }
                     };
                     auto pack_row = [&]() {
+                        float brow = 0.f;          // (a tile row's 8 values first: see the fp32 k-loop)
     #pragma unroll
                         for (int kk = 0; kk < 8; ++kk) {
-                            bsum += ra[kk];
+                            brow += ra[kk];
                             ca[kk] = (__bf16)ra[kk];
     #pragma unroll
                             for (int j = 0; j < J; ++j) cb[j][kk] = (__bf16)rb[kk][j];
                         }
+                        bsum += brow;
                     };
                     read_row();
                     pack_row();
@@ -724,6 +730,9 @@ wgrad_tile_kernel(const WgK ga) {
                 for (int j = 0; j < J; ++j) fb[0][j] = smem[xo[j]];
     #pragma unroll 1
                 for (int r = 0; r < ROWS; ++r) {
+                    // the bias sum takes a tile row's 8 values first and adds that to the running sum: one chain over all pixels of a split
+                    // (256 adds at four 8-row tiles) was 4 x the error of a pairwise fp32 sum (tests/test_gpu_wgrad_edges.py)
+                    float brow = 0.f;
     #pragma unroll
                     for (int k = 0; k < TWG / 2; ++k) {
                         const int cur = k & 1, nxt = cur ^ 1;
@@ -734,12 +743,13 @@ wgrad_tile_kernel(const WgK ga) {
     #pragma unroll
                         for (int j = 0; j < J; ++j) fb[nxt][j] = smem[xo[j] + xoff];
                         __builtin_amdgcn_sched_barrier(0);
-                        bsum += fa[cur];
+                        brow += fa[cur];
     #pragma unroll
                         for (int j = 0; j < J; ++j)
                             acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur], fb[cur][j], acc[j], 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
                     }
+                    bsum += brow;
                     go += TWG * COB;
     #pragma unroll
                     for (int j = 0; j < J; ++j) xo[j] += WT * CIB;
