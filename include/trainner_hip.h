@@ -714,6 +714,41 @@ int tnr_adam_step(float *p, const float *g, float *m, float *v, int64_t n, float
  * left untouched -- a step whose activations came out of a timed-out tile hand-off is never applied. */
 int tnr_adam_step_guarded(float *p, const float *g, float *m, float *v, int64_t n, float step_size, double b1,
                           double b2, float bc2_sqrt, float eps, float weight_decay, const uint32_t *fault, void *stream);
+/* --- the other optimisers of optimizers.py:100-129 over a flat buffer (csrc/optimizers.hip) ---
+ * chunks [nchunks][3] int64 = {offset, count <= 1024, segment}; segs [nseg][6] int64 = {offset, numel, rows (size(0) when dim() > 1,
+ * else 0), row length, dim(), first row index or -1}; rowseg [nrows] int32 = segment of every row.  Only the elements the chunks
+ * name are read or written.  Every launch that writes p or state sits behind *fault as tnr_adam_step_guarded (fault may be NULL).
+ * ws: tnr_optim_workspace_bytes(nseg, nrows) bytes.  Launches per call: sgd / rmsprop / madgrad 1, ranger 2, adamp / sgdp 4. */
+int64_t tnr_optim_workspace_bytes(int32_t nseg, int64_t nrows);
+/* torch.optim.SGD (lr, momentum, weight_decay); buf NULL <=> momentum == 0 */
+int tnr_sgd_step_guarded(float *p, const float *g, float *buf, const int64_t *chunks, int32_t nchunks, float lr, float momentum,
+                         float weight_decay, const uint32_t *fault, void *stream);
+/* torch.optim.RMSprop, not centered, no momentum */
+int tnr_rmsprop_step_guarded(float *p, const float *g, float *square_avg, const int64_t *chunks, int32_t nchunks, float lr,
+                             double alpha, float eps, float weight_decay, const uint32_t *fault, void *stream);
+/* MADGRAD (madgrad.py:85-179): lamb = (lr + eps) sqrt(k + 1); decay_mul = 1 - (lr + eps) decay (the 'AdamW' decay, adamw != 0);
+ * x0 NULL <=> momentum == 0 */
+int tnr_madgrad_step_guarded(float *p, const float *g, float *grad_sum_sq, float *s, const float *x0, const int64_t *chunks,
+                             int32_t nchunks, float lamb, float eps, float decay, float decay_mul, int32_t adamw, double momentum,
+                             const uint32_t *fault, void *stream);
+/* AdamP (adamp.py:45-134): step_size = lr / bias_correction1; decay_1 / decay_r = 1 - lr wd {1, wd_ratio}.  The projection decision
+ * (per output channel, else whole tensor, else none) is taken on the device. */
+int tnr_adamp_step_guarded(float *p, const float *g, float *m, float *v, const int64_t *chunks, int32_t nchunks, const int64_t *segs,
+                           int32_t nseg, const int32_t *rowseg, int64_t nrows, void *ws, int64_t ws_bytes, float step_size, double b1,
+                           double b2, float bc2_sqrt, float eps, int32_t nesterov, double delta, float weight_decay, float decay_1,
+                           float decay_r, const uint32_t *fault, void *stream);
+/* SGDP (sgdp.py:40-108): decay_1 / decay_r = 1 - lr wd {1, wd_ratio} / (1 - momentum).  Without Nesterov the reference's perturbation
+ * IS its momentum buffer, projected in place: buf then holds the projected perturbation, here as there. */
+int tnr_sgdp_step_guarded(float *p, const float *g, float *buf, const int64_t *chunks, int32_t nchunks, const int64_t *segs,
+                          int32_t nseg, const int32_t *rowseg, int64_t nrows, void *ws, int64_t ws_bytes, float lr, float momentum,
+                          double dampening, float eps, int32_t nesterov, double delta, float weight_decay, float decay_1,
+                          float decay_r, const uint32_t *fault, void *stream);
+/* Ranger (ranger.py:96-208): gradient centralisation of tensors with dim() > gc_min_dim, (rectified) Adam with step = step_size lr,
+ * and, when lookahead != 0, slow += alpha (p - slow); p = slow in the same launch */
+int tnr_ranger_step_guarded(float *p, const float *g, float *m, float *v, float *slow, const int64_t *chunks, int32_t nchunks,
+                            const int64_t *segs, int32_t nseg, const int32_t *rowseg, int64_t nrows, void *ws, int64_t ws_bytes,
+                            int32_t gc_min_dim, double b1, double b2, float eps, float weight_decay, float step, int32_t rectified,
+                            int32_t lookahead, float alpha, const uint32_t *fault, void *stream);
 /* Register ONE caller-owned, zero-initialised device word per process (one process drives one GPU) as the engine's fault latch:
  * the one-launch dense-block kernels (tnr_conv_chain, tnr_conv_sweep) set it to 1 when a bounded wait for a neighbouring tile gives
  * up (instead of the last word of their own workspace, which they use while no latch is registered).  Sticky: nothing in the

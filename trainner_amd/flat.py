@@ -14,9 +14,40 @@ import torch
 ALIGN = 64  # floats; keeps every parameter 256-B aligned
 
 
+CHUNK = 1024  # elements; what one block of an elementwise optimiser launch covers (csrc/optimizers.hip)
+
+
+class SegTable:
+    """The tensors of one flat buffer as the device tables of csrc/optimizers.hip.
+
+    entries: [(offset, shape)].  segs [nseg, 6] int64 = offset, numel, rows (size(0) when dim() > 1, else 0), row length, dim(), index
+    of the tensor's first row; chunks [nchunk, 3] int64 = offset, count (<= CHUNK), segment; rowseg [nrows] int32.  The launches walk
+    the chunks, so the alignment gaps between the tensors are never touched.  ws is the row-sum / decision workspace."""
+
+    def __init__(self, entries, device):
+        self.entries = [(int(o), tuple(int(d) for d in s)) for o, s in entries]
+        segs, chunks, rowseg, nrows = [], [], [], 0
+        for si, (off, shape) in enumerate(self.entries):
+            numel = 1
+            for d in shape:
+                numel *= d
+            rows = shape[0] if len(shape) > 1 else 0
+            segs.append((off, numel, rows, numel // rows if rows else numel, len(shape), nrows if rows else -1))
+            rowseg += [si] * rows
+            nrows += rows
+            for c in range(0, numel, CHUNK):
+                chunks.append((off + c, min(CHUNK, numel - c), si))
+        self.nseg, self.nchunks, self.nrows = len(segs), len(chunks), nrows
+        self.segs = torch.tensor(segs, dtype=torch.int64).reshape(-1, 6).to(device)
+        self.chunks = torch.tensor(chunks, dtype=torch.int64).reshape(-1, 3).to(device)
+        self.rowseg = torch.tensor(rowseg if rowseg else [0], dtype=torch.int32).to(device)
+        self.ws = torch.zeros(max(nrows, 1) * 40 + self.nseg * 16, dtype=torch.uint8, device=device)   # tnr_optim_workspace_bytes
+
+
 class FlatParams:
     def __init__(self, module):
         self.module = module
+        self._segs = None
         self.flat = None
         self.grad = None
         self.offsets = []   # (param, offset, numel)
@@ -72,8 +103,16 @@ class FlatParams:
                 p.grad = g
                 p._tnr_flat = (self, o)
         self.flat, self.grad = flat, grad
+        self._segs = None
         self.version += 1
         return self
+
+    def seg_table(self):
+        """The buffer's SegTable; rebuilt only after ensure() re-laid the buffer (touch() leaves it alone)."""
+        self.ensure()
+        if self._segs is None:
+            self._segs = SegTable([(o, p.shape) for p, o, n in self.offsets], self.flat.device)
+        return self._segs
 
     def view_of(self, p, which="grad"):
         holder, o = p._tnr_flat

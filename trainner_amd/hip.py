@@ -217,6 +217,16 @@ _SIGS = {
     "tnr_clip_by_norm": (c_i, [c_p, c_l, c_p, c_f, c_p]),
     "tnr_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, C.c_double, C.c_double, c_f, c_f, c_f, c_p]),
     "tnr_adam_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, C.c_double, C.c_double, c_f, c_f, c_f, c_p, c_p]),
+    "tnr_optim_workspace_bytes": (c_l, [c_i, c_l]),
+    "tnr_sgd_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_p, c_p]),
+    "tnr_rmsprop_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_i, c_f, C.c_double, c_f, c_f, c_p, c_p]),
+    "tnr_madgrad_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_f, c_i, C.c_double, c_p, c_p]),
+    "tnr_adamp_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_l, c_p, c_l, c_f, C.c_double, C.c_double, c_f, c_f,
+                                     c_i, C.c_double, c_f, c_f, c_f, c_p, c_p]),
+    "tnr_sgdp_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_l, c_p, c_l, c_f, c_f, C.c_double, c_f, c_i, C.c_double,
+                                    c_f, c_f, c_f, c_p, c_p]),
+    "tnr_ranger_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_l, c_p, c_l, c_i, C.c_double, C.c_double,
+                                      c_f, c_f, c_f, c_i, c_i, c_f, c_p, c_p]),
     "tnr_set_fault_word": (c_i, [c_p]),
 }
 

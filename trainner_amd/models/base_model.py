@@ -419,7 +419,7 @@ class BaseModel:
             tensors.append(net.flat_params().flat)
             tensors += [b for b in net.buffers() if b.is_floating_point() or b.dtype == torch.int64]
         for o in self.optimizers:
-            for mv in getattr(o, "_moments", {}).values():
+            for mv in getattr(o, "_moments", {}).values():       # EVERY flat state buffer of the optimiser (optimizers.FusedFlatOptimizer)
                 tensors += list(mv)
         # ESRGAN+ noise: ONE stream for all replicas (each rank draws the field of its own samples of the global batch): rank 0's
         # seed -- torch.initial_seed() differs per rank when manual_seed is unset -- and rank 0's position in the stream

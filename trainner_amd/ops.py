@@ -4,7 +4,7 @@ Nothing here computes with torch; torch only allocates the buffers the kernels r
 """
 import collections
 import ctypes as C
-
+import math
 import os
 
 import torch
@@ -1564,3 +1564,74 @@ def adam_step(p, g, m, v, step_size, b1, b2, bc2_sqrt, eps, wd=0.0):
     NOT applied (the weights stay those of the last healthy step until check_engine_errors() raises)."""
     hip.check(hip.load().tnr_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step_size, b1,
                                                b2, bc2_sqrt, eps, wd, fault_word(p.device).data_ptr(), hip.stream()), "adam_step")
+
+
+# ---------------------------------------------------------------------------------- the optimisers beside Adam (csrc/optimizers.hip)
+# `table` is the flat buffer's SegTable (trainner_amd/flat.py).  Hyper-parameters arrive as the reference's classes name them; the few
+# per-step scalars (bias corrections, N_sma, lamb) are formed here in Python doubles exactly as those classes form them.
+def _tbl(table):
+    return table.chunks.data_ptr(), table.nchunks
+
+
+def _tbl_rows(table):
+    need = hip.load().tnr_optim_workspace_bytes(table.nseg, table.nrows)
+    assert table.ws.numel() >= need, "SegTable workspace is smaller than tnr_optim_workspace_bytes"
+    return (table.chunks.data_ptr(), table.nchunks, table.segs.data_ptr(), table.nseg, table.rowseg.data_ptr(), table.nrows,
+            table.ws.data_ptr(), table.ws.numel())
+
+
+def sgd_step(p, g, buf, table, lr, momentum=0.0, wd=0.0):
+    """torch.optim.SGD over a flat buffer, one launch behind the fault latch.  buf is None exactly when momentum is 0."""
+    hip.check(hip.load().tnr_sgd_step_guarded(p.data_ptr(), g.data_ptr(), hip.ptr(buf), *_tbl(table), lr, momentum, wd,
+                                              fault_word(p.device).data_ptr(), hip.stream()), "sgd_step")
+
+
+def rmsprop_step(p, g, square_avg, table, lr, alpha, eps, wd=0.0):
+    """torch.optim.RMSprop (not centered, no momentum) over a flat buffer, one launch behind the fault latch."""
+    hip.check(hip.load().tnr_rmsprop_step_guarded(p.data_ptr(), g.data_ptr(), square_avg.data_ptr(), *_tbl(table), lr, alpha, eps, wd,
+                                                  fault_word(p.device).data_ptr(), hip.stream()), "rmsprop_step")
+
+
+def madgrad_step(p, g, grad_sum_sq, s, x0, table, lr, eps, k, momentum, decay=0.0, decay_type="AdamW"):
+    """MADGRAD step number k (0-based) over a flat buffer, one launch behind the fault latch.  x0 is None exactly when momentum is 0."""
+    lr = lr + eps                                   # the reference's own quirk (madgrad.py:87)
+    lamb = lr * math.pow(k + 1, 0.5)
+    hip.check(hip.load().tnr_madgrad_step_guarded(p.data_ptr(), g.data_ptr(), grad_sum_sq.data_ptr(), s.data_ptr(), hip.ptr(x0), *_tbl(table),
+                                                  lamb, eps, decay, 1 - lr * decay, int(decay_type == "AdamW"), momentum,
+                                                  fault_word(p.device).data_ptr(), hip.stream()), "madgrad_step")
+
+
+def adamp_step(p, g, m, v, table, lr, b1, b2, eps, t, nesterov=False, delta=0.1, wd_ratio=0.1, wd=0.0):
+    """AdamP step number t (1-based) over a flat buffer: 4 launches, the projection decision stays on the device."""
+    hip.check(hip.load().tnr_adamp_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), *_tbl_rows(table),
+                                                lr / (1 - b1 ** t), b1, b2, math.sqrt(1 - b2 ** t), eps, int(bool(nesterov)), delta, wd,
+                                                1 - lr * wd * 1, 1 - lr * wd * wd_ratio, fault_word(p.device).data_ptr(), hip.stream()),
+              "adamp_step")
+
+
+def sgdp_step(p, g, buf, table, lr, momentum, dampening, eps, nesterov=False, delta=0.1, wd_ratio=0.1, wd=0.0):
+    """SGDP over a flat buffer: 4 launches, the projection decision stays on the device."""
+    hip.check(hip.load().tnr_sgdp_step_guarded(p.data_ptr(), g.data_ptr(), buf.data_ptr(), *_tbl_rows(table), lr, momentum, dampening, eps,
+                                               int(bool(nesterov)), delta, wd, 1 - lr * wd * 1 / (1 - momentum) if wd > 0 else 1.0,
+                                               1 - lr * wd * wd_ratio / (1 - momentum) if wd > 0 else 1.0,
+                                               fault_word(p.device).data_ptr(), hip.stream()), "sgdp_step")
+
+
+def ranger_scalars(t, b1, b2, nsma_threshold):
+    """(rectified, step_size) of Ranger's step t (ranger.py:162-175)."""
+    beta2_t = b2 ** t
+    n_max = 2 / (1 - b2) - 1
+    n_sma = n_max - 2 * t * beta2_t / (1 - beta2_t)
+    if n_sma > nsma_threshold:
+        return True, math.sqrt((1 - beta2_t) * (n_sma - 4) / (n_max - 4) * (n_sma - 2) / n_sma * n_max / (n_max - 2)) / (1 - b1 ** t)
+    return False, 1.0 / (1 - b1 ** t)
+
+
+def ranger_step(p, g, m, v, slow, table, lr, b1, b2, eps, wd, t, k=6, alpha=0.5, nsma_threshold=5, use_gc=True, gc_conv_only=False):
+    """Ranger step number t (1-based) over a flat buffer: the row means of the gradient, then one launch with the centralised gradient,
+    the (rectified) Adam update and, on every k-th step, the lookahead."""
+    rect, step_size = ranger_scalars(t, b1, b2, nsma_threshold)
+    gc_min_dim = (3 if gc_conv_only else 1) if use_gc else (1 << 30)
+    hip.check(hip.load().tnr_ranger_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), slow.data_ptr(), *_tbl_rows(table),
+                                                 gc_min_dim, b1, b2, eps, wd, step_size * lr, int(rect), int(t % k == 0), alpha,
+                                                 fault_word(p.device).data_ptr(), hip.stream()), "ranger_step")
