@@ -60,8 +60,13 @@ enum {
     TNR_PACK_COL_DGRAD3 = 5,/* [1][KoutP=ci][KinP = k*k*Cout]: column t*Cout+co <- W[co][ci][k-1-ty][k-1-tx]  */
                             /* (any square k: the stride-1 data-gradient as im2col(g, pad k-1-p) x this)   */
     TNR_PACK_C4_FWD = 6,    /* [1][KoutP][48]: column 4*t + ci (Cin <= 4)        for TNR_CONV_3x3_C4             */
-    TNR_PACK_C4_DGRAD3 = 7  /* [1][KoutP=ci][48]: column 4*t + co (Cout <= 4), taps flipped                     */
+    TNR_PACK_C4_DGRAD3 = 7, /* [1][KoutP=ci][48]: column 4*t + co (Cout <= 4), taps flipped                     */
                             /* (both also with kh = kw = 7: [..][208] for TNR_CONV_7x7_C4)                     */
+    /* A 3x3 layer behind nearest x2 (block.py:326-371) as the virtual 4x4 s2 p1 convolution S it is the data-gradient of:
+     * W_S[ci][co][ky][kx] = sum of W[co][ci][ty][tx] over ty in T(ky), tx in T(kx), T = {2}, {1,2}, {0,1}, {0} (tnr_upconv_fold_table;
+     * fp32, added inside a row over ascending tx first, then the rows over ascending ty).  Both are made straight from the 3x3 tensor: */
+    TNR_PACK_UP2_DGRAD_S2 = 8, /* TNR_PACK_DGRAD_S2's layout of S, [4 parities][4][KoutP=co][KinP=ci]: the layer's FORWARD as TNR_DGRAD_4x4_S2 */
+    TNR_PACK_UP2_FWD_S2D = 9   /* TNR_PACK_FWD_S2D's layout of S, [4][KoutP=ci][4*KinP=co]: its DATA-GRADIENT (the x2 sum included) as TNR_CONV_4x4_S2 */
 };
 
 #define TNR_MMA_F32 0
@@ -209,6 +214,14 @@ int tnr_pack_dims(int32_t Cout, int32_t Cin, int32_t kh, int32_t kw, int32_t kin
                   int32_t *KoutP, int32_t *KinP, int64_t *n_out);
 /* items: DEVICE array of n descriptors; max_out = max n_out over the items */
 int tnr_pack_weights(const tnr_pack_item *items_dev, int32_t n, int64_t max_out, void *stream);
+/* The fold of the two TNR_PACK_UP2_* packings as a 16 x 9 matrix of 0 / 1 (host only, no launch): out[(ky*4 + kx)*9 + ty*3 + tx] = 1
+ * where 3x3 tap (ty, tx) is summed into folded tap (ky, kx).  Its transpose takes the weight gradient of S back to the 3x3 taps:     */
+int tnr_upconv_fold_table(int32_t out[144]);
+/* dw3[co][ci][3][3] = beta*dw3 + alpha * unfold(dws[ci][co][4][4]): the weight gradient of a nearest-x2 3x3 layer from the weight
+ * gradient of its folded S (tnr_conv_wgrad in TNR_CONV_4x4_S2 with x := gradient of the layer's output, g := the layer's input;
+ * aten::convolution_backward(weight) of upconv_block's conv, block.py:326-371).  Per tap three fp32 additions in a fixed order
+ * (inside a row of dws over ascending kx, then the two rows over ascending ky); one thread per (co, ci).  dws 16-byte aligned.        */
+int tnr_upconv_wgrad_unfold(const float *dws, float *dw3, int32_t Cout, int32_t Cin, float alpha, float beta, void *stream);
 int tnr_pack_dense_dims(int32_t nf, int32_t gc, int32_t t, int32_t *KoutP, int32_t *KinP, int64_t *n_out);
 int tnr_pack_dense_dgrad(const tnr_dense_pack_item *items_dev, int32_t n, int64_t max_out, void *stream);
 int tnr_conv_forward(const tnr_conv_desc *d, void *stream);

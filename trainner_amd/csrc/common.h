@@ -58,6 +58,27 @@ static inline int tnr_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t tnr_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int tnr_round_up(int a, int b) { return tnr_cdiv(a, b) * b; }
 
+// Nearest x2 in front of a 3x3 s1 p1 convolution is the data-gradient of a virtual 4x4 s2 p1 convolution S whose 16 taps fold the 9
+// (DESIGN.md 3.12).  Per axis, folded tap k = 0..3 sums the 3x3 taps tnr_upfold_lo(k) .. tnr_upfold_hi(k): {2}, {1,2}, {0,1}, {0}.
+__host__ __device__ inline int tnr_upfold_lo(int k) { return k == 0 ? 2 : (k == 1 ? 1 : 0); }
+__host__ __device__ inline int tnr_upfold_hi(int k) { return k <= 1 ? 2 : (k == 2 ? 1 : 0); }
+// F[ky][kx] of the 3x3 filter w9, in ONE fp32 order: inside a row of the 3x3 filter over ascending kx first, then the row sums over ascending ky.
+__host__ __device__ inline float tnr_upfold_tap(const float *w9, int ky, int kx) {
+    const int ylo = tnr_upfold_lo(ky), yhi = tnr_upfold_hi(ky), xlo = tnr_upfold_lo(kx), xhi = tnr_upfold_hi(kx);
+    float r0 = w9[ylo * 3 + xlo];
+    if (xhi != xlo) r0 = r0 + w9[ylo * 3 + xhi];
+    if (yhi == ylo) return r0;
+    float r1 = w9[yhi * 3 + xlo];
+    if (xhi != xlo) r1 = r1 + w9[yhi * 3 + xhi];
+    return r0 + r1;
+}
+// The transpose: gradient of 3x3 tap (ty, tx) from the 16 gradients dF of the folded taps -- folded taps 2 - t and 3 - t per axis -- in
+// the same order: inside a row of dF over ascending kx first, then the two rows over ascending ky.
+__host__ __device__ inline float tnr_upfold_grad(const float *dF16, int ty, int tx) {
+    const int ky = 2 - ty, kx = 2 - tx;
+    return (dF16[ky * 4 + kx] + dF16[ky * 4 + kx + 1]) + (dF16[(ky + 1) * 4 + kx] + dF16[(ky + 1) * 4 + kx + 1]);
+}
+
 // The fixed-order fp64 sum of a 256-thread block (`sh`: 256 doubles of LDS); the result is valid in thread 0.  Every reduction of
 // the library ends in it: two runs add in the same order and are bit-identical.
 __device__ __forceinline__ double tnr_block_sum256(double v, double *sh) {

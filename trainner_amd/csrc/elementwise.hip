@@ -384,6 +384,29 @@ __global__ void fill_kernel(float *p, int64_t n, float v) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) p[e] = v;
 }
 
+// One thread per (co, ci) filter: the 16 folded-tap gradients dws[ci][co][4][4] -> the 9 tap gradients dw3[co][ci][3][3]
+// (tnr_upfold_grad: a fixed order of three fp32 additions per tap).
+__global__ void upconv_wgrad_unfold_kernel(const float *dws, float *dw3, int Cout, int Cin, float alpha, float beta) {
+    const int total = Cout * Cin;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const int co = e / Cin, ci = e - co * Cin;
+        float dF[16];
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(dws + ((size_t)ci * Cout + co) * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 v = src[q];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dF[4 * q + k] = v[k];
+        }
+        float *dst = dw3 + (size_t)e * 9;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const float prev = (beta != 0.f) ? beta * dst[t] : 0.f;
+            dst[t] = prev + alpha * tnr_upfold_grad(dF, t / 3, t % 3);
+        }
+    }
+}
+
 inline bool view_ok(const tnr_view &v) { return v.ptr != nullptr && (v.ctot % 4) == 0 && (v.coff % 4) == 0; }
 
 }  // namespace
@@ -414,6 +437,15 @@ extern "C" int tnr_upsample2x_bwd(tnr_view gup, tnr_view gx, int32_t N, int32_t 
     hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(ew_grid(total)), dim3(EW_BLOCK), 0, (hipStream_t)stream, gup.ptr, gup.ctot,
                        gup.coff, gx.ptr, gx.ctot, gx.coff, N, H, W, C, mask.ptr, mask.ctot, mask.coff, mslope);
     return tnr_check_launch("upsample2x_bwd");
+}
+
+extern "C" int tnr_upconv_wgrad_unfold(const float *dws, float *dw3, int32_t Cout, int32_t Cin, float alpha, float beta, void *stream) {
+    TNR_REQUIRE(dws != nullptr && dw3 != nullptr && Cout > 0 && Cin > 0 && (int64_t)Cout * Cin < (1LL << 26),
+                "upconv_wgrad_unfold: bad arguments (%d -> %d channels)", Cin, Cout);
+    TNR_REQUIRE((reinterpret_cast<uintptr_t>(dws) & 15) == 0, "upconv_wgrad_unfold: the folded gradient must be 16-byte aligned");
+    hipLaunchKernelGGL(upconv_wgrad_unfold_kernel, dim3(ew_grid((int64_t)Cout * Cin)), dim3(EW_BLOCK), 0, (hipStream_t)stream, dws, dw3,
+                       Cout, Cin, alpha, beta);
+    return tnr_check_launch("upconv_wgrad_unfold");
 }
 
 extern "C" int tnr_depth_to_space(tnr_view x, tnr_view y, int32_t N, int32_t H, int32_t W, int32_t Cout, void *stream) {

@@ -74,6 +74,16 @@ extern "C" int tnr_pack_dims(int32_t Cout, int32_t Cin, int32_t kh, int32_t kw, 
             ko = tnr_round_up(Cin, 32); ki = tnr_round_up(4 * kh * kw, TNR_CK);
             n = (int64_t)ko * ki;
             break;
+        case TNR_PACK_UP2_DGRAD_S2:   // the folded S has Cout_S = Cin, Cin_S = Cout: its data-gradient produces the layer's Cout channels
+            TNR_REQUIRE(kh == 3 && kw == 3, "pack up2 dgrad s2: kernel must be 3x3");
+            ko = tnr_round_up(Cout, 32); ki = tnr_round_up(Cin, TNR_CK);
+            n = (int64_t)16 * ko * ki;
+            break;
+        case TNR_PACK_UP2_FWD_S2D:    // S itself produces the layer's Cin channels from its Cout
+            TNR_REQUIRE(kh == 3 && kw == 3, "pack up2 s2d: kernel must be 3x3");
+            ko = tnr_round_up(Cin, 32); ki = tnr_round_up(Cout, TNR_CK);
+            n = (int64_t)4 * ko * 4 * ki;
+            break;
         default:
             tnr_set_error("pack: bad kind %d", kind);
             return TNR_EINVAL;
@@ -131,6 +141,24 @@ __global__ void pack_weights_kernel(const tnr_pack_item *items) {
             const int ci = (int)(e / ki);
             const int t = v_ >> 2, co = v_ & 3;
             if (ci < Cin && t < kh * kw && co < Cout) v = it.w[(((size_t)co * Cin + ci) * kh + (kh - 1 - t / kw)) * kw + (kw - 1 - t % kw)];
+        } else if (it.kind == TNR_PACK_UP2_DGRAD_S2) {   // TNR_PACK_DGRAD_S2's layout of the folded S: [par][t][co][ci], W_S[ci][co] = fold(w[co][ci])
+            const int ci = (int)(e % ki);              // reduction channel = the 3x3 layer's input
+            int64_t q = e / ki;
+            const int co = (int)(q % ko);              // produced channel = the 3x3 layer's output
+            q /= ko;
+            const int t = (int)(q & 3);
+            const int par = (int)(q >> 2);
+            const int py = par >> 1, px = par & 1;
+            const int ky = ((py + 1) & 1) + 2 * (t >> 1), kx = ((px + 1) & 1) + 2 * (t & 1);
+            if (co < Cout && ci < Cin) v = tnr_upfold_tap(it.w + ((size_t)co * Cin + ci) * 9, ky, kx);
+        } else if (it.kind == TNR_PACK_UP2_FWD_S2D) {    // TNR_PACK_FWD_S2D's layout of the folded S: [t][ci][pp][co]
+            const int vch = (int)(e % (4 * ki));
+            int64_t q = e / (4 * ki);
+            const int ci = (int)(q % ko);              // produced channel = the 3x3 layer's input
+            const int t = (int)(q / ko);
+            const int pp = vch / ki, co = vch - pp * ki;   // reduction channel = the 3x3 layer's output
+            const int ky = 2 * (t >> 1) + (pp >> 1), kx = 2 * (t & 1) + (pp & 1);
+            if (co < Cout && ci < Cin) v = tnr_upfold_tap(it.w + ((size_t)co * Cin + ci) * 9, ky, kx);
         } else {  // TNR_PACK_DGRAD_S2: [par][t][ci][co]
             const int co = (int)(e % ki);
             int64_t q = e / ki;
@@ -195,6 +223,16 @@ extern "C" int tnr_pack_dense_dgrad(const tnr_dense_pack_item *items_dev, int32_
     if (bx < 1) bx = 1;
     hipLaunchKernelGGL(pack_dense_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, items_dev);
     return tnr_check_launch("pack_dense_dgrad");
+}
+
+extern "C" int tnr_upconv_fold_table(int32_t out[144]) {
+    TNR_REQUIRE(out != nullptr, "upconv_fold_table: null pointer");
+    for (int k = 0; k < 16; ++k)
+        for (int t = 0; t < 9; ++t) {
+            const int ky = k >> 2, kx = k & 3, ty = t / 3, tx = t % 3;
+            out[k * 9 + t] = ty >= tnr_upfold_lo(ky) && ty <= tnr_upfold_hi(ky) && tx >= tnr_upfold_lo(kx) && tx <= tnr_upfold_hi(kx);
+        }
+    return TNR_OK;
 }
 
 extern "C" int tnr_pack_weights(const tnr_pack_item *items_dev, int32_t n, int64_t max_out, void *stream) {

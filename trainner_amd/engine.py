@@ -25,6 +25,10 @@ class ConvOp:
             raise NotImplementedError("conv k=%d s=%d is not on the SR hot path" % (k, s))
         self.i_f = packer.add(mod.weight, pf)
         self.i_d = packer.add(mod.weight, pd) if need_dgrad else None
+        # nearest x2 + 3x3: the layer folded into its virtual 4x4 stride-2 convolution (ops.upconv_plan decides per pass and per call)
+        self.ups = ups
+        self.i_uf = packer.add(mod.weight, ops.PACK_UP2_DGRAD_S2) if ups else None
+        self.i_ud = packer.add(mod.weight, ops.PACK_UP2_FWD_S2D) if (ups and need_dgrad) else None
         # deep layers that can meet a tiny spatial extent (discriminator tail): column-layout packings for the
         # im2col + split-K GEMM path (ops.conv_small)
         deep = mod.in_channels * k * k >= 2048 and not ups
@@ -58,6 +62,13 @@ class ConvOp:
         epi["bias"] = self.mod.bias
         self._run(False, x, y, epi)
 
+    def fwd_up2(self, x, y, **epi):
+        """An UP2 layer's forward in the form ops.upconv_plan names: folded, one four-tap stride-2 data-gradient launch over the folded
+        weights (bias, activation and slope as in fwd); else fwd itself, the TNR_CONV_3x3_UP2 launch."""
+        if "fwd" not in ops.upconv_plan(x)[0]:
+            return self.fwd(x, y, **epi)
+        ops.conv(x, self.packer.get(self.i_uf), y, mode=ops.DGRAD_4x4_S2, family=ops.UPFOLD_FAMILY, bias=self.mod.bias, **epi)
+
     def fwd_shuffle2(self, x, y, **epi):
         """This layer + nn.PixelShuffle(2) in one launch, y = the shuffled tensor (ops.conv_shuffle2); False: not available here."""
         return ops.conv_shuffle2(x, self.packer.get(self.i_f), y, layer=self.dirs[False][1], bias=self.mod.bias, **epi)
@@ -65,6 +76,30 @@ class ConvOp:
     def dgrad(self, g, gx, **epi):
         """gx = conv_transpose(g); for an UP2 layer gx lives in the up-sampled domain."""
         self._run(True, g, gx, epi)
+
+    def dgrad_up2(self, g, gx, mask=None, m_slope=0.2):
+        """An UP2 layer's gradient in the LOW-resolution domain: gx = the 2 x 2 block sums of conv_transpose(g), times LeakyReLU'(mask)
+        where the layer's input is an activation's output.  Folded: one four-tap stride-2 launch with the mask in its epilogue; else
+        the 3x3 data-gradient into a high-resolution scratch and tnr_upsample2x_bwd."""
+        if "dgrad" in ops.upconv_plan(gx)[0]:
+            epi = dict(mask=mask, m_slope=m_slope) if mask is not None else {}
+            ops.conv(g, self.packer.get(self.i_ud), gx, mode=ops.CONV_4x4_S2, family=ops.UPFOLD_FAMILY, **epi)
+            return
+        gup = ops.View(ops.new_act(g.N, g.H, g.W, gx.C, g.buf.device))
+        self.dgrad(g, gup)
+        ops.upsample2x_bwd(gup, gx, mask=mask, mslope=m_slope)
+
+    def _wgrad_up2_folded(self, x, g, alpha, with_bias):
+        """dW (+ db) += alpha * ... of an UP2 layer through the folded S: its weight gradient (x := g, g := x) into a workspace, the
+        16 -> 9 tap unfold, and the bias gradient as the plain sum of g (S's own bias sum would be the sum of x)."""
+        w, b = self.mod.weight, self.mod.bias
+        cout, cin = w.shape[0], w.shape[1]
+        n = cin * cout * 16
+        dws = ops.WS.get("upfold_dw@%x" % hip.stream(), n * 4, x.buf.device).view(torch.float32)[:n].view(cin, cout, 4, 4)
+        ops.wgrad_group([dict(x=g, g=x, dw=dws, db=None, alpha=1.0, beta=0.0)], mode=ops.CONV_4x4_S2, family=ops.UPFOLD_FAMILY)
+        ops.upconv_wgrad_unfold(dws, w.grad, alpha=alpha, beta=1.0)
+        if with_bias and b is not None:
+            ops.bias_grad(g, b.grad, alpha=alpha, beta=1.0)
 
     def fwd_stage(self, x, y, fresh_from=None, **epi):
         """Stage descriptor of this layer's forward for ops.conv_chain."""
@@ -77,6 +112,9 @@ class ConvOp:
         return dict(x=x, g=g, dw=w.grad, db=db, cin_begin=cin_begin, alpha=alpha, beta=1.0, reflect=reflect)
 
     def wgrad(self, x, g, alpha=1.0, cin_begin=0, with_bias=True, reflect=False):
+        if self.ups and cin_begin == 0 and not reflect and "wgrad" in ops.upconv_plan(x)[0]:
+            self._wgrad_up2_folded(x, g, alpha, with_bias)
+            return
         if reflect:           # ReflectionPad2d(1) in front of the layer (TNR_CONV_3x3 on the matrix cores only)
             ops.wgrad_group([self.wgrad_item(x, g, alpha, cin_begin, with_bias, reflect=True)], mode=self.mode_f)
             return

@@ -21,6 +21,7 @@ MMA_F32, MMA_BF16, MMA_BF16X3 = 0, 1, 2
 CONV_3x3, CONV_3x3_UP2, CONV_4x4_S2, DGRAD_4x4_S2, CONV_1x1, CONV_3x3_C4, CONV_7x7_C4 = 0, 1, 2, 3, 4, 5, 6
 PACK_FWD, PACK_DGRAD_3x3, PACK_FWD_S2D, PACK_DGRAD_S2, PACK_COL_FWD, PACK_COL_DGRAD3 = 0, 1, 2, 3, 4, 5
 PACK_C4_FWD, PACK_C4_DGRAD3 = 6, 7
+PACK_UP2_DGRAD_S2, PACK_UP2_FWD_S2D = 8, 9      # a nearest-x2 3x3 layer folded into its virtual 4x4 stride-2 convolution
 PACK_DENSE_DGRAD = 16      # host-side tag of tnr_pack_dense_dgrad slabs (consumed like PACK_FWD by conv_tile)
 
 
@@ -74,6 +75,8 @@ _SIGS = {
     "tnr_version": (c_i, []),
     "tnr_pack_dims": (c_i, [c_i, c_i, c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_l)]),
     "tnr_pack_weights": (c_i, [c_p, c_i, c_l, c_p]),
+    "tnr_upconv_fold_table": (c_i, [C.POINTER(c_i * 144)]),
+    "tnr_upconv_wgrad_unfold": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
     "tnr_pack_dense_dims": (c_i, [c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_l)]),
     "tnr_pack_dense_dgrad": (c_i, [c_p, c_i, c_l, c_p]),
     "tnr_conv_forward": (c_i, [C.POINTER(ConvDesc), c_p]),

@@ -153,7 +153,7 @@ class RRDBNet(HipNet):
             H2, W2 = cur.H * 2, cur.W * 2
             if self.upsample_mode == "upconv":
                 nxt = View(new_act(N, H2, W2, nf, dev))
-                u.fwd(cur, nxt, act=act, slope=sl)
+                u.fwd_up2(cur, nxt, act=act, slope=sl)
                 stages.append((cur, nxt, None))
             else:
                 nxt = View(new_act(N, H2, W2, nf, dev))
@@ -296,10 +296,8 @@ class RRDBNet(HipNet):
                 if W:
                     u.wgrad(src, gcur)
                     done(u)
-                gup = View(new_act(N, dst.H, dst.W, nf, dev))
-                u.dgrad(gcur, gup)
                 gsrc = View(new_act(N, src.H, src.W, nf, dev))
-                ops.upsample2x_bwd(gup, gsrc, mask=(src if prev_is_act else None), mslope=sl)
+                u.dgrad_up2(gcur, gsrc, mask=(src if prev_is_act else None), m_slope=sl)
             else:
                 gt = View(new_act(N, src.H, src.W, 4 * nf, dev))
                 ops.space_to_depth_bwd(gcur, gt, mask=dst, mslope=sl)

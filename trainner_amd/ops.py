@@ -11,7 +11,8 @@ import torch
 
 from . import hip
 from .hip import (ACT_LRELU, ACT_NONE, ACT_RELU, CONV_1x1, CONV_3x3, CONV_3x3_C4, CONV_3x3_UP2, CONV_4x4_S2, CONV_7x7_C4, DGRAD_4x4_S2,  # noqa: F401
-                  PACK_C4_DGRAD3, PACK_C4_FWD, PACK_COL_DGRAD3, PACK_COL_FWD, PACK_DENSE_DGRAD, PACK_DGRAD_3x3, PACK_DGRAD_S2, PACK_FWD, PACK_FWD_S2D, CView,
+                  PACK_C4_DGRAD3, PACK_C4_FWD, PACK_COL_DGRAD3, PACK_COL_FWD, PACK_DENSE_DGRAD, PACK_DGRAD_3x3, PACK_DGRAD_S2, PACK_FWD, PACK_FWD_S2D, PACK_UP2_DGRAD_S2,
+                  PACK_UP2_FWD_S2D, CView,
                   ConvDesc,
                   DensePackItem, PackItem, WgradDesc)
 
@@ -467,7 +468,7 @@ def conv_plan(x, wp, y, mode=CONV_3x3, epi=None, shuffle=0, layer=None, wino=Non
     return "tile", why
 
 
-def _conv_launch(x, wp, y, mode, wino, shuffle, epi, layer=None):
+def _conv_launch(x, wp, y, mode, wino, shuffle, epi, layer=None, family=None):
     """The one tnr_conv_forward path (conv, conv_shuffle2) -> the form launched; None: shuffle cannot be folded and nothing ran.  Descriptor; the
     library's late answers, each asked where conv_plan's answer hangs on it and fed back into the plan on a decline; the launch; the PROFILE record."""
     d, said = None, {}
@@ -506,7 +507,7 @@ def _conv_launch(x, wp, y, mode, wino, shuffle, epi, layer=None):
     hip.check(lib.tnr_conv_forward(C.byref(d), hip.stream()), "conv_forward")
     if PROFILE is not None:
         fam, taps = _CONV_FAMILY[mode]          # (the Winograd form: the algorithmic FLOP of the convolution it computes)
-        PROFILE.end("conv_wino_3x3" if form == "wino" else fam, 2.0 * d.N * d.Ho * d.Wo * taps * min(x.C, wp.KinP) * d.Cout, t0, (x.C, d.Cout, d.Ho, wp.kind))
+        PROFILE.end("conv_wino_3x3" if form == "wino" else (family or fam), 2.0 * d.N * d.Ho * d.Wo * taps * min(x.C, wp.KinP) * d.Cout, t0, (x.C, d.Cout, d.Ho, wp.kind))
     return form
 
 
@@ -517,10 +518,90 @@ def conv_shuffle2(x, wp, y, layer=None, **epi):
     return _conv_launch(x, wp, y, CONV_3x3, None, 2, epi, layer) is not None
 
 
-def conv(x, wp, y, mode=CONV_3x3, wino=None, **epi):
+def conv(x, wp, y, mode=CONV_3x3, wino=None, family=None, **epi):
     """One tnr_conv_forward launch in the form conv_plan names.  wino: None = the process policy (WINO and the layer's size), True / False =
-    force / forbid the Winograd form for this launch."""
-    _conv_launch(x, wp, y, mode, wino, 0, epi)
+    force / forbid the Winograd form for this launch.  family: the PROFILE family the launch is counted in instead of its mode's."""
+    _conv_launch(x, wp, y, mode, wino, 0, epi, family=family)
+
+
+# ----------------------------------------------------------------------------------------------
+# nearest x2 + 3x3 (upconv_block) folded into the four-tap stride-2 launches
+# ----------------------------------------------------------------------------------------------
+UPFOLD_FAMILY = "conv_upfold"           # PROFILE family of the folded launches (all three passes), counted with the FLOP they execute (16 taps)
+UPFOLD_PASSES = ("fwd", "dgrad", "wgrad")
+# per axis: the 3x3 taps summed into folded tap k = 0..3 (csrc/common.h tnr_upfold_lo / tnr_upfold_hi)
+UPFOLD_TAPS = ((2,), (1, 2), (0, 1), (0,))
+# The passes TNR_UPCONV_FOLD=1 folds (upconv_plan): both gradients, NOT the forward.  The folded forward is the more accurate form against
+# fp64 and 1.1 ms / step faster, but it moves the SR batch itself (1.7e-6 of its scale in the first step), and the GAN step amplifies a
+# change that enters there far more than one that enters through a gradient: after 25 benchmark steps the outputs stand 5.6 % of the SR
+# scale from the unfolded run's with it, 0.15 % without -- the process's two fp32 arithmetics stand 3.4 % apart (profiles/r30a_upconv_fold.txt).
+_UPFOLD_DEFAULT = ("dgrad", "wgrad")
+
+
+def upconv_plan(x, mma=_LIVE, switch=_LIVE):
+    """Which passes of ONE `Upsample(nearest, x2) -> Conv2d(3, 1, 1)` layer run folded right now -> (passes, reason); x: the layer's
+    LOW-resolution input view.  passes: the subset of UPFOLD_PASSES that runs as a four-tap stride-2 launch; the others keep the
+    present launches (TNR_CONV_3x3_UP2, the 3x3 data-gradient + tnr_upsample2x_bwd, the x2 weight-gradient class).  reason: None
+    when TNR_UPCONV_FOLD itself selects the passes, else why NOTHING is folded.
+    The fold: nearest x2 followed by a zero-padded 3x3 convolution is the data-gradient of a virtual 4x4 stride-2
+    padding-1 convolution S, W_S[ci][co] = the 16 sums of the 3x3 taps over {2}, {1,2}, {0,1}, {0} per axis, so
+      "fwd"    is one TNR_DGRAD_4x4_S2 launch over the TNR_PACK_UP2_DGRAD_S2 packing (bias, activation as before);
+      "dgrad"  is one TNR_CONV_4x4_S2 launch over the TNR_PACK_UP2_FWD_S2D packing: it sums the 2 x 2 block itself and carries the
+               previous activation's mask in its epilogue (tnr_upsample2x_bwd does not run);
+      "wgrad"  is the 4x4 stride-2 weight-gradient class into a workspace, tnr_upconv_wgrad_unfold (16 -> 9 taps), tnr_bias_grad.
+    16 instead of 36 products per output pixel and channel pair; the results differ from the present launches at rounding level
+    (weights summed before the product, 16 accumulation steps instead of 36) and are deterministic.
+    First matching row wins:
+      ((), "switch")       TNR_UPCONV_FOLD=0 (read at call time; switch=... asks a what-if).
+      ((), "arithmetic")   the arithmetic is not bf16x3: TNR_MMA=f32 is the CPU reference's bit-parity class and stays on
+                           TNR_CONV_3x3_UP2; `use_amp` (bf16 operands) stays there too -- one arithmetic question per change.
+      ((), "device")       x is not a device tensor (the CPU stand-in of the tests re-states the present launches).
+      (passes, None)       TNR_UPCONV_FOLD=1 (default): the passes of _UPFOLD_DEFAULT, i.e. the data gradient and the weight gradient -- the
+                           forward stays on TNR_CONV_3x3_UP2, so the network's outputs for given weights are bit for bit the unfolded
+                           ones; a comma list names the passes itself ("fwd,dgrad,wgrad": all three; A/B runs).
+    The folded launches are ordinary 4x4 stride-2 launches to conv_plan: they land on its "stream" / "tile" rows, the stream kernel's
+    decline for grids narrower than 32 pixels included."""
+    sw = os.environ.get("TNR_UPCONV_FOLD", "1") if switch is _LIVE else str(switch)
+    if sw == "0":
+        return (), "switch"
+    if (MMA if mma is _LIVE else mma) != hip.MMA_BF16X3:
+        return (), "arithmetic"
+    if not _on_device(x.buf):
+        return (), "device"
+    if sw == "1":
+        return _UPFOLD_DEFAULT, None
+    return tuple(p for p in UPFOLD_PASSES if p in sw.split(",")), None
+
+
+def upconv_fold_table():
+    """The library's 16 x 9 fold matrix (tnr_upconv_fold_table) as a float64 tensor: row ky*4 + kx, column ty*3 + tx."""
+    out = (C.c_int32 * 144)()
+    hip.check(hip.load().tnr_upconv_fold_table(C.byref(out)), "upconv_fold_table")
+    return torch.tensor(list(out), dtype=torch.float64).view(16, 9)
+
+
+def upconv_fold_weights(w):
+    """[..., 3, 3] -> the folded [..., 4, 4] taps in the library's fp32 order (tnr_upfold_tap): inside a row over ascending kx first,
+    then the row sums over ascending ky.  The channel swap of S is the packings' business, not this function's."""
+    rows = []
+    for ty in range(3):      # row sums: [..., 4] per 3x3 row
+        rows.append(torch.stack([w[..., ty, t[0]] if len(t) == 1 else w[..., ty, t[0]] + w[..., ty, t[1]] for t in UPFOLD_TAPS], dim=-1))
+    return torch.stack([rows[t[0]] if len(t) == 1 else rows[t[0]] + rows[t[1]] for t in UPFOLD_TAPS], dim=-2)
+
+
+def upconv_unfold_grad(dF):
+    """[..., 4, 4] gradients of the folded taps -> [..., 3, 3] in the library's fp32 order (tnr_upfold_grad): 3x3 tap t collects
+    folded taps 2 - t and 3 - t per axis, inside a row over ascending kx first, then the two rows over ascending ky."""
+    def row(ky):
+        return torch.stack([dF[..., ky, 2 - tx] + dF[..., ky, 3 - tx] for tx in range(3)], dim=-1)
+    return torch.stack([row(2 - ty) + row(3 - ty) for ty in range(3)], dim=-2)
+
+
+def upconv_wgrad_unfold(dws, dw3, alpha=1.0, beta=1.0):
+    """dw3 [Cout, Cin, 3, 3] = beta dw3 + alpha unfold(dws [Cin, Cout, 4, 4]) (tnr_upconv_wgrad_unfold)."""
+    Cout, Cin = dw3.shape[0], dw3.shape[1]
+    assert tuple(dws.shape) == (Cin, Cout, 4, 4) and dws.is_contiguous() and dw3.is_contiguous()
+    hip.check(hip.load().tnr_upconv_wgrad_unfold(dws.data_ptr(), dw3.data_ptr(), Cout, Cin, alpha, beta, hip.stream()), "upconv_wgrad_unfold")
 
 
 CHAIN_MAX = 6
@@ -960,9 +1041,10 @@ def wgrad(x, g, dw, db=None, mode=CONV_3x3, cin_begin=0, alpha=1.0, beta=1.0, re
     wgrad_group([dict(x=x, g=g, dw=dw, db=db, cin_begin=cin_begin, alpha=alpha, beta=beta, reflect=reflect)], mode=mode)
 
 
-def wgrad_group(items, mode=CONV_3x3):
+def wgrad_group(items, mode=CONV_3x3, family=None):
     """Several weight gradients of one pixel geometry and one workgroup tile class in a single launch
-    (tnr_conv_wgrad_group).  items: dicts with x, g, dw and optional db, cin_begin, alpha, beta, pair = (dw2, db2, cout_split)."""
+    (tnr_conv_wgrad_group).  items: dicts with x, g, dw and optional db, cin_begin, alpha, beta, pair = (dw2, db2, cout_split).
+    family: the PROFILE family the launch is counted in instead of "wgrad_tile"."""
     lib = hip.load()
     n = len(items)
     assert 1 <= n <= WGRAD_GROUP_MAX
@@ -983,7 +1065,7 @@ def wgrad_group(items, mode=CONV_3x3):
     taps = 16 if mode == CONV_4x4_S2 else 9
     x0, g0 = items[0]["x"], items[0]["g"]
     flops = sum(2.0 * it["g"].pixels * taps * it["x"].C * it["g"].C for it in items)
-    PROFILE.end("wgrad_tile", flops, t0, (sum(it["x"].C for it in items) if n > 1 else x0.C, g0.C, g0.H, mode + 100 * (n - 1)))
+    PROFILE.end(family or "wgrad_tile", flops, t0, (sum(it["x"].C for it in items) if n > 1 else x0.C, g0.C, g0.H, mode + 100 * (n - 1)))
 
 
 def wgrad_tile_class(desc, group_jobs=0, x3_occ=-1):
