@@ -594,6 +594,36 @@ int tnr_pointwise_loss_bwd(const float *a, const float *b, int64_t n, int32_t cr
 int tnr_overflow_loss_fwd(const float *x, int64_t n, double scale, float *loss, void *ws, void *stream);
 int tnr_overflow_loss_bwd(const float *x, int64_t n, double scale, const float *gscale, float *gx, int32_t accumulate, void *stream);
 
+/* --- pooled pixel losses (modules/loss.py ColorLoss :587-597, AverageLoss :601-609, MultiscalePixelLoss :431-454, L1CosineSim
+ * :364-384; csrc/pooled_losses.hip) ----------------------------------------------------------------------------------------------
+ * x (carries the gradient) and y: fp32 N x C x H x W with C <= 4, layout 0 = NCHW-contiguous, 1 = channels-last.  `crit`: one of the
+ * TNR_CRIT_* above over the difference, or TNR_CRIT_L1COS over the channel vector of one cell:
+ *   mean |a - b| over N C' H' W'  +  5 * mean over N H' W' of (1 - a / max(|a|, 1e-20) . b / max(|b|, 1e-20)); the clamp of a
+ *   zero-norm a passes no gradient to its norm.
+ * tnr_pool_loss_*: crit(M(P_k x), M(P_k y)), mean-reduced.  P_k = the k x k box average with stride k, k = 1 .. 8, floor mode: the
+ *   trailing H % k rows and W % k columns belong to no cell.  M = identity, or with `uv` != 0 (C == 3) the two BT.601 chroma planes
+ *   u = .493 (b - y) + .5, v = .877 (r - y) + .5 with y = .299 r + .587 g + .114 b (C' = 2).  No pooled image is stored.
+ * tnr_multiscale_loss_*: sum over the levels i = 0 .. 4 of w_i crit(x_i, y_i), w = 1, .5, .25, .125, .125, x_0 = x and
+ *   x_{i+1} = the 2 x 2 box average of x_i in floor mode (level i is floor(H / 2^i) x floor(W / 2^i)); every level's mean divides by
+ *   its own count.  min(H, W) >= 16.
+ * Every fwd is ONE launch: blocks leave fp64 partials in `ws` (tnr_pooled_workspace_bytes; its first 16 bytes are a ticket word
+ *   that must be zero before the first launch and is handed back at zero), the last block to arrive sums them in a fixed order and
+ *   writes loss[0].  Every bwd is one launch that recomputes the cells and writes (or adds to, `accumulate`) EVERY element of gx
+ *   (x's shape and layout, never x or y) = gscale[0] (NULL = 1) * d loss / dx: zeros where no cell covers the pixel. */
+enum { TNR_CRIT_L1COS = 5 };
+int64_t tnr_pooled_workspace_bytes(void);
+/* The largest grids of the two forwards (defaults 256 and 1024; a block takes several cells / bands beyond them): a process-wide
+ * override for measurements and for tests of the multi-band paths, not thread-safe; <= 0 restores a default.  At most 2048 / 4096. */
+int tnr_pooled_forward_blocks(int32_t pool_blocks, int32_t ms_blocks);
+int tnr_pool_loss_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t k, int32_t uv,
+                      int32_t crit, float *loss, void *ws, int64_t ws_bytes, void *stream);
+int tnr_pool_loss_bwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t k, int32_t uv,
+                      int32_t crit, const float *gscale, float *gx, int32_t accumulate, void *stream);
+int tnr_multiscale_loss_fwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t crit,
+                            float *loss, void *ws, int64_t ws_bytes, void *stream);
+int tnr_multiscale_loss_bwd(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t layout, int32_t crit,
+                            const float *gscale, float *gx, int32_t accumulate, void *stream);
+
 /* --- spatial profile losses (modules/loss.py SPLoss :741-757, GPLoss :616-649, CPLoss :652-707; csrc/spl_loss.hip) ------------------
  * SPLoss(D, E) = -(sum over every column of every (n, k) plane of cos(column of D, column of E) + the same over rows) / (H N), each
  * cosine as F.normalize forms it: D / max(|D|, 1e-12) . E / max(|E|, 1e-12).  x (carries the gradient) and y: fp32 N x C x H x W,

@@ -18,8 +18,6 @@
 
 namespace {
 
-enum { CRIT_L1 = TNR_CRIT_L1, CRIT_L2 = TNR_CRIT_L2, CRIT_CB = TNR_CRIT_CB, CRIT_ELASTIC = TNR_CRIT_ELASTIC, CRIT_CLIPL1 = TNR_CRIT_CLIPL1 };
-
 constexpr int FK = 15, FR = FK / 2;                      // filter taps per side (smaller odd filters are centred and zero-padded)
 constexpr int TW = 64, TH = 16;                          // tile of every stencil kernel; thread = 4 neighbouring columns of one row
 constexpr int FIW = TW + 2 * FR, FIH = TH + 2 * FR;      // 78 x 30 staged differences
@@ -29,30 +27,6 @@ constexpr int DST = TW + 3;                              // finite-difference ti
 struct FilterTaps {
     float w[FK * FK];
 };
-
-__device__ __forceinline__ float sgn(float e) { return e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f); }
-
-__device__ __forceinline__ float rho(float e, int crit) {
-    const float a = fabsf(e);
-    switch (crit) {
-    case CRIT_L1: return a;
-    case CRIT_L2: return e * e;
-    case CRIT_CB: return sqrtf(e * e + 1e-12f);
-    case CRIT_ELASTIC: return 0.2f * (e * e) + 0.8f * a;
-    default: return fminf(a, 10.f);                      // clipl1: clamp(|e|, 0, 10)
-    }
-}
-
-// d rho / d e as autograd gives it: sign(0) = 0, the clamp passes the gradient on the closed interval
-__device__ __forceinline__ float drho(float e, int crit) {
-    switch (crit) {
-    case CRIT_L1: return sgn(e);
-    case CRIT_L2: return 2.f * e;
-    case CRIT_CB: return e / sqrtf(e * e + 1e-12f);
-    case CRIT_ELASTIC: return 0.4f * e + 0.8f * sgn(e);
-    default: return fabsf(e) <= 10.f ? sgn(e) : 0.f;
-    }
-}
 
 __global__ __launch_bounds__(256) void sum_kernel(const double *__restrict__ partial, int64_t count, double scale, float *__restrict__ loss) {
     __shared__ double sh[256];

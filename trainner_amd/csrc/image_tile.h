@@ -1,6 +1,6 @@
-// What the image-loss translation units (ssim_loss.hip, image_losses.hip, freqsep.hip) share: the view of a dense fp32 image batch,
-// the argument checks and the 16-byte-path test of their entry points, the block -> tile decode, the staging of a tile with a zero
-// halo in LDS and the final sum over the blocks' fp64 partials.  The kernels stay in their files (DESIGN.md sections 11-13).
+// What the image-loss translation units (ssim_loss.hip, image_losses.hip, spl_loss.hip, pooled_losses.hip, freqsep.hip) share: the view
+// of a dense fp32 image batch, the argument checks and the 16-byte-path test of their entry points, the block -> tile decode, the staging
+// of a tile with a zero halo in LDS, the difference-only criteria and the final sum over the blocks' fp64 partials.  The kernels stay in their files (DESIGN.md sections 11-13).
 #pragma once
 #include "common.h"
 
@@ -92,6 +92,33 @@ __device__ __forceinline__ void stage_tile(const ImView &g, int64_t base, int y0
 #pragma unroll
             for (int t = 0; t < NT; ++t) dst[t][r * ST + q] = v[t];
         }
+    }
+}
+
+// The criteria of the difference alone (image_losses.hip, pooled_losses.hip): rho(e) and d rho / d e as autograd gives it
+// (sign(0) = 0, the clamp passes the gradient on the closed interval)
+enum { CRIT_L1 = TNR_CRIT_L1, CRIT_L2 = TNR_CRIT_L2, CRIT_CB = TNR_CRIT_CB, CRIT_ELASTIC = TNR_CRIT_ELASTIC, CRIT_CLIPL1 = TNR_CRIT_CLIPL1 };
+
+__device__ __forceinline__ float sgn(float e) { return e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f); }
+
+__device__ __forceinline__ float rho(float e, int crit) {
+    const float a = fabsf(e);
+    switch (crit) {
+    case CRIT_L1: return a;
+    case CRIT_L2: return e * e;
+    case CRIT_CB: return sqrtf(e * e + 1e-12f);
+    case CRIT_ELASTIC: return 0.2f * (e * e) + 0.8f * a;
+    default: return fminf(a, 10.f);                      // clipl1: clamp(|e|, 0, 10)
+    }
+}
+
+__device__ __forceinline__ float drho(float e, int crit) {
+    switch (crit) {
+    case CRIT_L1: return sgn(e);
+    case CRIT_L2: return 2.f * e;
+    case CRIT_CB: return e / sqrtf(e * e + 1e-12f);
+    case CRIT_ELASTIC: return 0.4f * e + 0.8f * sgn(e);
+    default: return fabsf(e) <= 10.f ? sgn(e) : 0.f;
     }
 }
 

@@ -190,6 +190,12 @@ _SIGS = {
     "tnr_pointwise_loss_bwd": (c_i, [c_p, c_p, c_l, c_i, C.c_double, c_p, c_p, c_i, c_p]),
     "tnr_overflow_loss_fwd": (c_i, [c_p, c_l, C.c_double, c_p, c_p, c_p]),
     "tnr_overflow_loss_bwd": (c_i, [c_p, c_l, C.c_double, c_p, c_p, c_i, c_p]),
+    "tnr_pooled_workspace_bytes": (c_l, []),
+    "tnr_pooled_forward_blocks": (c_i, [c_i, c_i]),
+    "tnr_pool_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_l, c_p]),
+    "tnr_pool_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
+    "tnr_multiscale_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_l, c_p]),
+    "tnr_multiscale_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
     "tnr_spl_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i]),
     "tnr_spl_coef_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i]),
     "tnr_spl_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_l, c_p]),

@@ -10,7 +10,9 @@ loss over any dictionary of layers (`perceptual_opt.perceptual_layers`) and the 
 (train_sr.yml:114-120): the difference-only pixel criteria l2, cb, elastic and clipl1, HFEN (`hfen_criterion` /
 `hfen_weight`), total variation (`tv_type` / `tv_norm` / `tv_weight`) and the image-gradient loss of the precise list
 (`grad_type` / `grad_weight`), and the first two experimental terms (train_sr.yml "Experimental losses"): the spatial profile losses
-(`spl_type: spl | cpl | gpl` / `spl_weight`) and the overflow loss (`of_type: overflow` / `of_weight`).  With frequency separation (`fs`, base_model.setup_fs) `GeneratorLoss` hands the low-passed images to
+(`spl_type: spl | cpl | gpl` / `spl_weight`), the overflow loss (`of_type: overflow` / `of_weight`) and the colour, averaging-downscale
+and multi-scale pixel losses (`color_criterion: color-<crit>` / `color_weight`, `avg_criterion: avg-<crit>` / `avg_weight`,
+`ms_criterion: multiscale-<crit>` / `ms_weight`, <crit> one of l1, l2, cb, elastic, clipl1, l1cosinesim).  With frequency separation (`fs`, base_model.setup_fs) `GeneratorLoss` hands the low-passed images to
 the colour / content terms and `Adversarial` shows the discriminator the high-pass residual (dataops/filters.py).  Anything else
 raises NotImplementedError (no silent fallback to eager PyTorch).
 """
@@ -22,6 +24,7 @@ from ..dataops import diffaug as diffaug_ops
 from ..dataops import filters
 from . import networks
 from .modules import image_losses as IL
+from .modules import pooled_losses as PL
 from .modules import spl as SPL
 from .modules._dense import dense_layout, gscale
 from .modules.ssim import MS_SSIM, SSIM
@@ -187,6 +190,10 @@ def get_loss_fn(loss_type=None, weight=0, recurrent=False, reduction="mean", net
     elif loss_type in ("MSE", "l2", "cb", "elastic", "clipl1"):
         loss_function = IL.criterion(loss_type, reduction)
         loss_type = "pix-{}".format(loss_type)
+    elif loss_type is not None and loss_type.find("multiscale") >= 0:
+        # losses.py:59-64: multiscale-<criterion>, named as a pixel loss (so frequency separation hands it the low-passed pair)
+        loss_function = PL.MultiscalePixelLoss(loss_f=PL.inner_criterion(_inner_name(loss_type)))
+        loss_type = "pix-{}".format(loss_type)
     elif loss_type is not None and loss_type.find("hfen") >= 0:
         # losses.py:86-92: the criterion is asked for with reduction='sum' (cb and clipl1 ignore it and stay means)
         loss_function = IL.HFENLoss(loss_f=IL.criterion(loss_type.split("-")[1], "sum"))
@@ -229,11 +236,25 @@ def get_loss_fn(loss_type=None, weight=0, recurrent=False, reduction="mean", net
         image_channels = ((opt or {}).get("image_channels") or 3) if allow_featnets else 1
         kw = dict(window_size=11, window_sigma=1.5, size_average=True, data_range=1., channels=image_channels)
         loss_function = SSIM(**kw) if loss_type in ("ssim", "SSIM") else MS_SSIM(normalize="relu", **kw)
+    elif loss_type is not None and (loss_type.find("color") >= 0 or loss_type.find("avg") >= 0):
+        # losses.py:146-155: color-<criterion> | avg-<criterion> on the AvgPool2d(kernel_size=opt['scale']) images
+        if not (opt or {}).get("scale"):
+            raise ValueError("Loss type [{}] needs the model's `scale` option for its pool".format(loss_type))
+        cls = PL.ColorLoss if loss_type.find("color") >= 0 else PL.AverageLoss
+        loss_function = cls(loss_f=PL.inner_criterion(_inner_name(loss_type)), ds_f=nn.AvgPool2d(kernel_size=opt["scale"]))
     else:
         raise NotImplementedError("Loss type [{}] is not implemented by the HIP engine".format(loss_type))
     if recurrent:
         return loss_function.to(device)
     return {"name": loss_type, "weight": weight, "function": loss_function.to(device)}
+
+
+def _inner_name(loss_type):
+    """<criterion> of color-<criterion> / avg-<criterion> / multiscale-<criterion>."""
+    parts = loss_type.split("-")
+    if len(parts) != 2:
+        raise NotImplementedError("Loss type [{}] is not implemented by the HIP engine".format(loss_type))
+    return parts[1]
 
 
 def check_loss_names(feature_criterion=None, feature_network=None, hfen_criterion=None, tv_type=None, tv_norm=None, **_unused):
@@ -412,12 +433,14 @@ def ops_mean(pred):
 
 
 class GeneratorLoss(nn.Module):
-    """Weighted list of generator losses (losses.py:607-962): pixel, hfen, tv, contextual, feature, cpl, gpl, overflow, then the
-    precise list grad, ssim; same order and names."""
+    """Weighted list of generator losses (losses.py:607-962): pixel, hfen, tv, contextual, feature, cpl, gpl, overflow, colour,
+    average, multi-scale, then the precise list grad, ssim; same order and names."""
 
-    _UNSUPPORTED = ("color_weight", "avg_weight", "ms_weight",
-                    "lpips_weight", "fft_weight",
+    _UNSUPPORTED = ("lpips_weight", "fft_weight",
                     "fdpl_weight", "range_weight")
+    # losses.py:633-640,775-788: weight key, criterion key, the family its criterion must name
+    _POOLED = (("color_weight", "color_criterion", "color"), ("avg_weight", "avg_criterion", "avg"),
+               ("ms_weight", "ms_criterion", "multiscale"))
 
     def __init__(self, opt=None, device="cpu", allow_featnets=True):
         super().__init__()
@@ -429,6 +452,9 @@ class GeneratorLoss(nn.Module):
         pixel_criterion = train_opt.get("pixel_criterion", None)
         self.loss_list = []
         if pixel_weight > 0 and pixel_criterion:
+            if pixel_criterion.find("multiscale") >= 0:
+                raise NotImplementedError("pixel_criterion [{}] is not implemented by the HIP engine: the multi-scale pixel loss is "
+                                          "built from ms_criterion / ms_weight".format(pixel_criterion))
             self.loss_list.append(get_loss_fn(pixel_criterion, pixel_weight, device=device))
         hfen_weight = train_opt.get("hfen_weight", 0) or 0
         hfen_criterion = check_loss_names(hfen_criterion=train_opt.get("hfen_criterion"))
@@ -463,6 +489,20 @@ class GeneratorLoss(nn.Module):
         of_type = train_opt.get("of_type", None)
         if of_weight > 0 and of_type:
             self.loss_list.append(get_loss_fn(of_type, of_weight, device=device))
+        # losses.py:775-788: colour, average, multi-scale, in this order.  A criterion without a weight builds nothing, as in the
+        # reference; a weight without its criterion is refused (stricter than the reference, which silently builds nothing), like
+        # grad_weight below
+        for wkey, ckey, family in self._POOLED:
+            weight = train_opt.get(wkey, 0) or 0
+            crit = train_opt.get(ckey, None)
+            if weight > 0 and not crit:
+                raise NotImplementedError("loss option '{}' is set but '{}' is not: give {} ({}-<criterion>) or drop the "
+                                          "weight".format(wkey, ckey, ckey, family))
+            if weight > 0:
+                if crit.find(family) < 0:
+                    raise NotImplementedError("{} [{}] is not implemented by the HIP engine (expected {}-<criterion>)".format(
+                        ckey, crit, family))
+                self.loss_list.append(get_loss_fn(crit, weight, opt=opt, device=device))
         # the "precise" terms (losses.py:780-816), evaluated by the models after the GAN term and always in fp32
         self.precise_loss_list = []
         grad_weight = train_opt.get("grad_weight", 0) or 0
@@ -509,7 +549,9 @@ class GeneratorLoss(nn.Module):
         # under data parallelism the logged value is the global-batch mean, as the reference computes it on the gathered batch.
         # The gradient needs no extra collective: every term here but the sum-reduced HFEN ones (see _effective) is a batch mean
         # over equal shards, so averaging the ranks' gradients makes it the global-batch gradient.  cpl, gpl and overflow are such
-        # means too (SPLoss divides its per-image line cosines by the batch size): no collective, no world-size factor
+        # means too (SPLoss divides its per-image line cosines by the batch size): no collective, no world-size factor.  So are the
+        # colour, average and multi-scale terms: every pooled cell belongs to one image and each level's mean (the cosine term of
+        # l1cosinesim included) divides by a count proportional to the batch size
         log_dict[name] = self.dp_group.mean_scalar(effective) if self.dp_group is not None else effective.detach()
 
     @staticmethod
@@ -588,7 +630,8 @@ class GeneratorLoss(nn.Module):
                 effective = self._effective(l, l["function"](self._fp32(sr)))              # fake_H alone
             elif l["name"] == "contextual":
                 effective = l["weight"] * self._contextual(l["function"], sr, hr)
-            elif l["name"] in ("cpl", "gpl") or isinstance(l["function"], (IL.HFENLoss, IL._Criterion)):
+            elif (l["name"] in ("cpl", "gpl") or l["name"].split("-")[0] in ("color", "avg") or "pix-multiscale" in l["name"]
+                  or isinstance(l["function"], (IL.HFENLoss, IL._Criterion))):
                 effective = self._effective(l, l["function"](self._fp32(sr), self._fp32(hr)))   # fp32 kernels with or without AMP
             else:
                 effective = l["weight"] * l["function"](sr, hr)

@@ -1432,6 +1432,64 @@ def overflow_loss_bwd(x, scale, gscale, gx, accumulate=False):
                                                hip.stream()), "overflow_loss_bwd")
 
 
+# Pooled pixel losses (csrc/pooled_losses.hip): crit over k x k box averages (with `uv` over their two BT.601 chroma planes), and the
+# five-level multi-scale sum.  crit: a CRIT_* above or CRIT_L1COS (over the channel vector of a cell).  One launch each way; the
+# forwards' workspace starts with a ticket word that the kernels expect and leave at zero, so it is allocated zeroed and kept per
+# stream handle.  The trade-off: zeroing the word before every forward would be a second enqueue per loss, which the one-launch form
+# exists to avoid; instead a forward whose call reports an error drops its workspace, so the next one starts from a fresh zeroed
+# buffer.  A launch that dies on the device without an error from the call takes the context with it.  A stream handle reused after
+# its stream was destroyed gets the old buffer back, whose ticket is zero between launches.
+CRIT_L1COS = 5
+_POOLED_WS = {}
+
+
+def _pooled_ws(x):
+    key = (hip.stream(), str(x.device))
+    t = _POOLED_WS.get(key)
+    if t is None:
+        t = _POOLED_WS[key] = torch.zeros(hip.load().tnr_pooled_workspace_bytes() // 8 + 1, dtype=torch.float64, device=x.device)
+    return key, t
+
+
+def _pooled_check(rc, key, what):
+    if rc != 0:
+        _POOLED_WS.pop(key, None)
+    hip.check(rc, what)
+
+
+def pooled_forward_blocks(pool_blocks=0, ms_blocks=0):
+    """The largest grids of the two forwards, process-wide (0: the default): for measurements and tests of the multi-band paths."""
+    hip.check(hip.load().tnr_pooled_forward_blocks(int(pool_blocks), int(ms_blocks)), "pooled_forward_blocks")
+
+
+def pool_loss_fwd(x, y, layout, k, uv, crit, loss):
+    """loss (1 float) = the mean-reduced crit of the k x k box averages of x and y (`uv`: of their chroma planes, C == 3)."""
+    N, Ch, H, W = x.shape
+    key, ws = _pooled_ws(x)
+    _pooled_check(hip.load().tnr_pool_loss_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, int(k), int(bool(uv)), crit, loss.data_ptr(),
+                                               ws.data_ptr(), ws.numel() * 8, hip.stream()), key, "pool_loss_fwd")
+
+
+def pool_loss_bwd(x, y, layout, k, uv, crit, gscale, gx, accumulate=False):
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_pool_loss_bwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, int(k), int(bool(uv)), crit, hip.ptr(gscale),
+                                           gx.data_ptr(), int(accumulate), hip.stream()), "pool_loss_bwd")
+
+
+def multiscale_loss_fwd(x, y, layout, crit, loss):
+    """loss (1 float) = sum over five levels of w_i * the mean-reduced crit of the 2^i x 2^i box averages, w = 1, .5, .25, .125, .125."""
+    N, Ch, H, W = x.shape
+    key, ws = _pooled_ws(x)
+    _pooled_check(hip.load().tnr_multiscale_loss_fwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, crit, loss.data_ptr(), ws.data_ptr(),
+                                                     ws.numel() * 8, hip.stream()), key, "multiscale_loss_fwd")
+
+
+def multiscale_loss_bwd(x, y, layout, crit, gscale, gx, accumulate=False):
+    N, Ch, H, W = x.shape
+    hip.check(hip.load().tnr_multiscale_loss_bwd(x.data_ptr(), y.data_ptr(), N, Ch, H, W, layout, crit, hip.ptr(gscale), gx.data_ptr(),
+                                                 int(accumulate), hip.stream()), "multiscale_loss_bwd")
+
+
 # Spatial profile losses (csrc/spl_loss.hip).  mask: the families of derived planes the SPLoss traces run on; loss: 5 floats, one per
 # family in the order of the bits and their sum; coef (spl_coef): the per-line backward coefficients the forward leaves.
 SPL_RGB, SPL_YUV, SPL_DIMG, SPL_DYUV = 1, 2, 4, 8
