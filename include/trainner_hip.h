@@ -239,6 +239,17 @@ int tnr_conv_wq_pack(const tnr_conv_desc *d, void *image, int64_t image_bytes, v
  * Cin % 16 == 0, TNR_MMA_BF16X3, stride 1, zero or reflection padding (nn.Conv2d k3 s1 p1, block.py:214-256; ResNet_arch.py:118-146). */
 int64_t tnr_conv_wino_bytes(const tnr_conv_desc *d);
 int tnr_conv_wino_pack(const tnr_conv_desc *d, void *image, int64_t image_bytes, void *stream);
+/* nn.MaxPool2d(2, 2) behind the convolution's activation folded into the STORE of a Winograd-form launch, whose 2 x 2 output patch is the
+ * pool window: d describes the unpooled launch (Ho = H, Wo = W, wq_form = 1) except that d->y is the POOLED tensor [N, Ho / 2, Wo / 2, Cout];
+ * the full-resolution map never exists.  The stored value is bit for bit what tnr_maxpool2_fwd computes from the map tnr_conv_forward
+ * would have stored (window scan order (0,0), (0,1), (1,0), (1,1), `v > best`: the first maximum wins).  route: NULL, or a dense
+ * [N, Ho / 2, Wo / 2, Cout] byte map that receives per pooled element bits 0-1 = the arg-max position under that rule and bit 2 = "pooled
+ * value > 0" -- everything tnr_maxpool2_bwd derives from the full-resolution map (tnr_unpool2_bwd takes the byte instead).
+ * tnr_conv_pool_ok: 1 when the launch qualifies -- the Winograd form (tnr_conv_wino_bytes > 0), H and W even, ReLU or no activation, no
+ * r1 / r2 / mask / noise / shuffle / split-K workspace --, else 0: the caller then runs tnr_conv_forward and tnr_maxpool2_fwd.
+ * The request travels as arguments of an entry of its own, not as descriptor members: tnr_conv_desc keeps its layout (ABI 3).          */
+int tnr_conv_pool_ok(const tnr_conv_desc *d);
+int tnr_conv_forward_pool2(const tnr_conv_desc *d, uint8_t *route, void *stream);
 /* out[(n*Ho + oy)*Wo + ox][(ky*kw + kx)*C + c] = x[n][oy*stride - pad + ky][ox*stride - pad + kx][c] (0 outside):
  * the patch matrix of a k x k convolution as an NHWC "image" of Ho*Wo*N pixels with kh*kw*C channels, for
  * TNR_CONV_1x1 with TNR_PACK_COL_* weights.  C % 4 == 0.                                                */
@@ -468,6 +479,10 @@ int tnr_space_to_depth_bwd(tnr_view gy, tnr_view gx, int32_t N, int32_t H, int32
 int tnr_maxpool2_fwd(tnr_view x, tnr_view y, int32_t N, int32_t H, int32_t W, int32_t C, void *stream);
 int tnr_maxpool2_bwd(tnr_view gy, tnr_view x, tnr_view gx, int32_t N, int32_t H, int32_t W, int32_t C,
                      void *stream);
+/* tnr_maxpool2_bwd from the byte map of tnr_conv_forward_pool2 instead of the full-resolution activation: gx[N, H, W, C] gets gy[N, H / 2,
+ * W / 2, C] at the window position in bits 0-1 of the element's byte when bit 2 is set, zeros everywhere else (bit-identical to
+ * tnr_maxpool2_bwd on the map the unfused launch stores).  map: dense [N, H / 2, W / 2, C] bytes, 4-byte aligned.                       */
+int tnr_unpool2_bwd(tnr_view gy, const uint8_t *map, tnr_view gx, int32_t N, int32_t H, int32_t W, int32_t C, void *stream);
 int tnr_axpby(tnr_view dst, tnr_view src, int64_t pixels, int32_t C, float a, float b, void *stream);
 int tnr_mask_mul(tnr_view g, tnr_view y, int64_t pixels, int32_t C, float mslope, void *stream);
 int tnr_fill(float *p, int64_t n, float v, void *stream);

@@ -5,6 +5,31 @@
 
 namespace {
 
+// The 4 x 4 transpose inside a quad of lanes (position qb = b0 + 2 b1): two butterfly stages of DPP quad_perm moves.
+__device__ __forceinline__ void tnr_quad_transpose(float &v0, float &v1, float &v2, float &v3, const bool b0, const bool b1) {
+    // stage 1: exchange with lane ^ 1 inside pairs (v0,v1), (v2,v3); stage 2: with lane ^ 2 inside (v0,v2), (v1,v3)
+    auto xchg = [&](float &x, float &y, bool sel, int which) {
+        const float send = sel ? x : y;
+        const int r_ = which == 1 ? __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true)    // quad_perm:[1,0,3,2]
+                                  : __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, true);   // quad_perm:[2,3,0,1]
+        const float recv = __builtin_bit_cast(float, r_);
+        x = sel ? recv : x;
+        y = sel ? y : recv;
+    };
+    xchg(v0, v1, b0, 1);
+    xchg(v2, v3, b0, 1);
+    xchg(v0, v2, b1, 2);
+    xchg(v1, v3, b1, 2);
+}
+
+// act(acc + bias) * alpha of one float4; ns: act(v) = max(v, 0) + ns * min(v, 0).  Every epilogue below goes through this line.
+__device__ __forceinline__ f32x4 tnr_bias_act4(const f32x4 acc, const f32x4 bv, const float ns, const float alpha) {
+    f32x4 v = acc + bv;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(ns, __builtin_fminf(v[e], 0.f), __builtin_fmaxf(v[e], 0.f)) * alpha;
+    return v;
+}
+
 // Epilogue of a tile (the quad-transpose epilogue of conv_body.h as a function: same arithmetic, same order): `acc` holds the MFMA
 // results of wave `wave` (M-tile mi = pixels (wave * MT + mi) * 32 .. + 31 of the TW-wide tile at (ty0, tx0), channel block cb).
 // PixFn: (mi, row 0 .. 31 of that M-tile) -> (tile row, tile column) of the pixel that accumulator row holds.  The default is the row-major
@@ -33,21 +58,7 @@ __device__ __forceinline__ void conv_epilogue_dpp_map(const ConvK a, f32x16 (&ac
 #endif
     const int qa = li >> 2, qb = li & 3;               // quad index a (channel quad), position b inside the quad
     const bool b0 = (qb & 1) != 0, b1 = (qb & 2) != 0;
-    auto quad_transpose = [&](float &v0, float &v1, float &v2, float &v3) {
-        // stage 1: exchange with lane ^ 1 inside pairs (v0,v1), (v2,v3); stage 2: with lane ^ 2 inside (v0,v2), (v1,v3)
-        auto xchg = [&](float &x, float &y, bool sel, int which) {
-            const float send = sel ? x : y;
-            const int r_ = which == 1 ? __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true)    // quad_perm:[1,0,3,2]
-                                      : __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, true);   // quad_perm:[2,3,0,1]
-            const float recv = __builtin_bit_cast(float, r_);
-            x = sel ? recv : x;
-            y = sel ? y : recv;
-        };
-        xchg(v0, v1, b0, 1);
-        xchg(v2, v3, b0, 1);
-        xchg(v0, v2, b1, 2);
-        xchg(v1, v3, b1, 2);
-    };
+    auto quad_transpose = [&](float &v0, float &v1, float &v2, float &v3) { tnr_quad_transpose(v0, v1, v2, v3, b0, b1); };
     TNR_STAMP(5);
     TNR_STAMP(6);
     TNR_STAMP(7);
@@ -134,9 +145,7 @@ __device__ __forceinline__ void conv_epilogue_dpp_map(const ConvK a, f32x16 (&ac
         for (int nn = 0; nn < NT; ++nn) {
             float v0 = acc[mi][nn][4 * q + 0], v1 = acc[mi][nn][4 * q + 1], v2 = acc[mi][nn][4 * q + 2], v3 = acc[mi][nn][4 * q + 3];
             quad_transpose(v0, v1, v2, v3);
-            f32x4 v = f32x4{v0, v1, v2, v3} + bv[nn];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(ns, __builtin_fminf(v[e], 0.f), __builtin_fmaxf(v[e], 0.f)) * a.alpha;
+            f32x4 v = tnr_bias_act4(f32x4{v0, v1, v2, v3}, bv[nn], ns, a.alpha);
             if (has_r1) v += b1f[nn] * q1[set][nn];
             if (has_noise) {           // (its own branch: the paths without noise keep their instruction stream)
                 const f32x4 nm = tnr_gauss_mult4(((unsigned)pixi[set] + a.noise_pix0) * (unsigned)(a.Cout >> 2) + (unsigned)(co_n[nn] >> 2),
@@ -178,6 +187,60 @@ __device__ __forceinline__ void conv_epilogue_dpp_map(const ConvK a, f32x16 (&ac
     for (int u = 0; u < UNITS; ++u) {
         if (u + AHEAD < UNITS) prep(u + AHEAD, (u + AHEAD) % SETS);
         finish(u, u % SETS);
+    }
+}
+
+// The pooled store: y = maxpool2x2(act(acc + bias) * alpha), for kernels whose waves hold whole 2 x 2 output windows (conv_wino.hip).
+// win[k][4 qq + e]: accumulator register 4 (q0 + qq) + e (the MFMA result layout above, one 32-channel block `cb`) of window position
+// k = 2 dy + dx.  Every position goes through the quad transpose and tnr_bias_act4 exactly like in conv_epilogue_dpp_map, so the four
+// values are the ones the unfused launch stores; they are then scanned in the order k = 0 .. 3 with `v > best` -- the first maximum
+// wins: maxpool2_fwd_kernel's rule -- and one float4 goes to pixel (ty0 / 2 + pr, tx0 / 2 + pc) of the [N, Ho / 2, Wo / 2] view `a.y`,
+// (pr, pc) = patchfn(accumulator row).  `route` (optional, dense [N, Ho / 2, Wo / 2, Cout] bytes): bits 0-1 = the arg-max k, bit 2 =
+// pooled value > 0 -- what maxpool2_bwd_kernel derives from the full-resolution map (tnr_unpool2_bwd routes a gradient by it).
+// Cout % 32 == 0, Ho and Wo even, ReLU or no activation, no residual / mask / noise operands (tnr_conv_pool_ok).
+template <int QN, class PatchFn>
+__device__ __forceinline__ void conv_epilogue_pool2(const ConvK a, unsigned char *route, const float (&win)[4][QN * 4], const int q0,
+                                                    const int cb, const int n, const int ty0, const int tx0, const int li, const int half,
+                                                    PatchFn &&patchfn) {
+    const int qa = li >> 2, qb = li & 3;
+    const bool b0 = (qb & 1) != 0, b1 = (qb & 2) != 0;
+    const float ns = a.act == TNR_ACT_LRELU ? a.slope : (a.act == TNR_ACT_RELU ? 0.f : 1.f);
+    const int co = cb * 32 + qa * 4;
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (a.bias != nullptr) bv = *reinterpret_cast<const f32x4 *>(a.bias + co);
+    const int Hp = a.Ho >> 1, Wp = a.Wo >> 1;
+#pragma unroll
+    for (int qq = 0; qq < QN; ++qq) {
+        int pr, pc;
+        patchfn(8 * (q0 + qq) + 4 * half + qb, pr, pc);
+        const int py = (ty0 >> 1) + pr, px = (tx0 >> 1) + pc;
+        f32x4 best;
+        unsigned arg[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float v0 = win[k][4 * qq + 0], v1 = win[k][4 * qq + 1], v2 = win[k][4 * qq + 2], v3 = win[k][4 * qq + 3];
+            tnr_quad_transpose(v0, v1, v2, v3, b0, b1);
+            const f32x4 v = tnr_bias_act4(f32x4{v0, v1, v2, v3}, bv, ns, a.alpha);
+            if (k == 0) {
+                best = v;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool gt = v[e] > best[e];
+                    best[e] = gt ? v[e] : best[e];
+                    arg[e] = gt ? (unsigned)k : arg[e];
+                }
+            }
+        }
+        if (!(py < Hp && px < Wp)) continue;          // (a ragged tile: even sizes keep a window wholly inside or wholly outside)
+        const size_t pix = ((size_t)n * Hp + py) * Wp + px;
+        *reinterpret_cast<f32x4 *>(a.y + pix * a.y_ct + a.y_co + co) = best;
+        if (route != nullptr) {
+            unsigned w = 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w |= (arg[e] | (best[e] > 0.f ? 4u : 0u)) << (8 * e);
+            *reinterpret_cast<unsigned *>(route + pix * a.Cout + co) = w;
+        }
     }
 }
 

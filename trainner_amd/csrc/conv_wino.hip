@@ -75,6 +75,8 @@ struct WinoK {
     int wq_bytes;
     int nck;                           // input chunks (Cin / 16)
     int tiles_x, tiles_y, ncb, tiles;
+    int pool;                          // 2: the store is maxpool2x2 of the activated output, a.y the [N, Ho / 2, Wo / 2] view (tnr_conv_forward_pool2)
+    unsigned char *route;              // with pool: the optional arg-max / sign byte map (conv_epilogue_pool2)
 };
 
 struct WinoPackK {
@@ -452,6 +454,32 @@ __global__ void __launch_bounds__(512, 2) conv3x3_wino_kernel(const WinoK c) {
                 }
         }
         __syncthreads();
+        if (c.pool != 0) {
+            // ---- the pooled store (wave-uniform branch): the 2 x 2 output patch IS the pool window.  Here a wave finishes BOTH output rows
+            // of half of the accumulator registers (r = 8 il .. 8 il + 7) of M-tile m = h, N-tile nt -- by the row step's own two formulas,
+            // so every value is the one the plain store writes -- and conv_epilogue_pool2 stores the window's maximum (+ the route byte)
+            float win[4][8];             // [2 k + l][r - 8 il]
+            auto slot = [&](int ip, int l) __attribute__((always_inline)) {
+                return smem + (((ip >> 1) * 4 + wn * 2 + (ip & 1)) * 4 + l * 2 + wh) * (16 * 64) + wil * (8 * 64) + lane;
+            };
+#pragma unroll
+            for (int l = 0; l < 2; ++l) {
+                const float *p0 = slot(0, l), *p1 = slot(1, l), *p2 = slot(2, l), *p3 = slot(3, l);
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const float x0 = p0[r * 64], x1 = p1[r * 64], x2 = p2[r * 64], x3 = p3[r * 64];
+                    win[l][r] = (x0 + x1) + x2;
+                    win[2 + l][r] = (x1 - x2) - x3;
+                }
+            }
+            conv_epilogue_pool2<2>(a, c.route, win, 2 * wil, cb * 2 + wn, n, ty0, tx0, li, half,
+                                   [&](int row, int &pr, int &pc) __attribute__((always_inline)) {
+                                       const int p = 32 * wh + row;
+                                       pr = p >> 3;
+                                       pc = p & 7;
+                                   });
+            continue;
+        }
         // this wave finishes output row k = w & 1 of the patches of M-tile m = h, couts of N-tile nt: rows i' = k, k + 1, k + 2 of the four
         // waves (h', il') of its N-tile, i' = 2 h' + il' -> wave index (i' >> 1) * 4 + nt * 2 + (i' & 1)
         f32x16 keep[2][1];
@@ -759,19 +787,53 @@ extern "C" int tnr_conv_wino_pack(const tnr_conv_desc *d, void *image, int64_t i
     return tnr_check_launch("conv_wino_pack");
 }
 
-// called by tnr_conv_forward (conv_tile.hip) for a launch whose weight stream is the transform-domain one (wq_form = 1); 1: not for this kernel
-int tnr_launch_conv3x3_wino(const tnr_conv_desc *d, void *stream) {
+namespace {
+
+bool wino16_requested() {
+    static const bool w16 = [] { const char *e = getenv("TNR_WINO_WAVES"); return e != nullptr && atoi(e) == 16; }();
+    return w16;
+}
+
+// pool: 0 = the plain store, 2 = the pooled one (d->y the [N, Ho / 2, Wo / 2] view, route optional); 1: not for this kernel
+int launch_wino(const tnr_conv_desc *d, int pool, unsigned char *route, void *stream) {
     if (!wino_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wino_bytes(d) || d->noise_pos < 0 || d->noise_pos > 2) return 1;
     static int cus = 0;
     if (const int rc = tnr_kernel_setup(&cus, "conv3x3_wino", {{conv3x3_wino_kernel, WN_LDS_BYTES}, {conv3x3_wino16_kernel, WN_LDS_BYTES}})) return rc;
     WinoK c;
     if (!stream_k_from_desc(c, *d, tnr_conv_wino_bytes(d), WN_T, WN_T, 1)) return 1;
+    c.pool = pool;
+    c.route = route;
     const int grid = c.tiles < cus ? c.tiles : cus;
-    static const bool w16 = [] { const char *e = getenv("TNR_WINO_WAVES"); return e != nullptr && atoi(e) == 16; }();
+    const bool w16 = wino16_requested();
+    if (w16 && pool != 0) return 1;          // (the sixteen-wave probe has no pooled store)
     if (w16) {
         hipLaunchKernelGGL(conv3x3_wino16_kernel, dim3((unsigned)grid), dim3(1024), WN_LDS_BYTES, (hipStream_t)stream, c);
         return tnr_check_launch("conv3x3_wino16");
     }
     hipLaunchKernelGGL(conv3x3_wino_kernel, dim3((unsigned)grid), dim3(512), WN_LDS_BYTES, (hipStream_t)stream, c);
     return tnr_check_launch("conv3x3_wino");
+}
+
+}  // namespace
+
+// called by tnr_conv_forward (conv_tile.hip) for a launch whose weight stream is the transform-domain one (wq_form = 1); 1: not for this kernel
+int tnr_launch_conv3x3_wino(const tnr_conv_desc *d, void *stream) { return launch_wino(d, 0, nullptr, stream); }
+
+// Can this launch store maxpool2x2 of its activated output instead of the output (tnr_conv_forward_pool2)?  The Winograd form's answer:
+// its 2 x 2 output patch is the pool window.  d describes the UNPOOLED launch (Ho = H, Wo = W); every other form declines.
+extern "C" int tnr_conv_pool_ok(const tnr_conv_desc *d) {
+    return d != nullptr && wino_ok(d) && !wino16_requested() && (d->H % 2) == 0 && (d->W % 2) == 0 &&
+           (d->act == TNR_ACT_RELU || d->act == TNR_ACT_NONE) && d->r1.ptr == nullptr && d->r2.ptr == nullptr && d->m.ptr == nullptr &&
+           d->noise_pos == 0 && d->shuffle == 0 && d->ws == nullptr && views_aligned(*d);
+}
+
+extern "C" int tnr_conv_forward_pool2(const tnr_conv_desc *d, uint8_t *route, void *stream) {
+    TNR_REQUIRE(d != nullptr && d->x.ptr && d->y.ptr && d->wp, "conv_forward_pool2: null pointer");
+    TNR_REQUIRE(tnr_conv_pool_ok(d), "conv_forward_pool2: the launch cannot store its pooled output (tnr_conv_pool_ok() == 0)");
+    TNR_REQUIRE(d->wq != nullptr && d->wq_form == 1 && d->wq_bytes >= tnr_conv_wino_bytes(d),
+                "conv_forward_pool2: needs the transform-domain weight stream (tnr_conv_wino_pack, wq_form = 1)");
+    TNR_REQUIRE((reinterpret_cast<uintptr_t>(route) & 3) == 0, "conv_forward_pool2: the route map must be 4-byte aligned");
+    const int rc = launch_wino(d, 2, route, stream);
+    TNR_REQUIRE(rc != 1, "conv_forward_pool2: the launch does not qualify for the Winograd kernel");
+    return rc;
 }

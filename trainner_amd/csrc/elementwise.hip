@@ -214,6 +214,39 @@ __global__ void maxpool2_bwd_kernel(const float *gy, int g_ct, int g_co, const f
     }
 }
 
+// maxpool2_bwd_kernel with the route bytes of the pooled convolution store (conv_epilogue.h conv_epilogue_pool2) in place of the
+// full-resolution activation: per pooled element bits 0-1 = the arg-max position k, bit 2 = pooled value > 0.  One thread per
+// (pooled pixel, channel quad): one float4 of gradient and four map bytes in, four float4 out.
+__global__ void unpool2_bwd_kernel(const float *gy, int g_ct, int g_co, const unsigned char *map, float *gx, int gx_ct, int gx_co, int N,
+                                   int H, int W, int C) {
+    const int Ho = H / 2, Wo = W / 2, c4n = C / 4;
+    const int64_t total = (int64_t)N * Ho * Wo * c4n;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const int c4 = (int)(e % c4n);
+        const int64_t pix = e / c4n;
+        const int ox = (int)(pix % Wo);
+        const int64_t q = pix / Wo;
+        const int oy = (int)(q % Ho);
+        const int64_t n = q / Ho;
+        const f32x4 g = *reinterpret_cast<const f32x4 *>(gy + pix * g_ct + g_co + c4 * 4);
+        const unsigned mw = *reinterpret_cast<const unsigned *>(map + pix * C + c4 * 4);
+        f32x4 o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned b = (mw >> (8 * j)) & 0xffu;
+            const int arg = (int)(b & 3u);
+            const bool on = (b & 4u) != 0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k][j] = (k == arg && on) ? g[j] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t ip = (n * H + 2 * oy + (k >> 1)) * W + 2 * ox + (k & 1);
+            *reinterpret_cast<f32x4 *>(gx + ip * gx_ct + gx_co + c4 * 4) = o[k];
+        }
+    }
+}
+
 __global__ void axpby_kernel(float *dst, int d_ct, int d_co, const float *src, int s_ct, int s_co, int64_t pixels, int C,
                              float a, float b) {
     const int c4n = C / 4;
@@ -480,6 +513,15 @@ extern "C" int tnr_maxpool2_bwd(tnr_view gy, tnr_view x, tnr_view gx, int32_t N,
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total)), dim3(EW_BLOCK), 0, (hipStream_t)stream, gy.ptr, gy.ctot,
                        gy.coff, x.ptr, x.ctot, x.coff, gx.ptr, gx.ctot, gx.coff, N, H, W, C);
     return tnr_check_launch("maxpool2_bwd");
+}
+
+extern "C" int tnr_unpool2_bwd(tnr_view gy, const uint8_t *map, tnr_view gx, int32_t N, int32_t H, int32_t W, int32_t C, void *stream) {
+    TNR_REQUIRE(view_ok(gy) && view_ok(gx) && map != nullptr && (reinterpret_cast<uintptr_t>(map) & 3) == 0 && N > 0 && H > 0 && W > 0 && C > 0 &&
+                (C % 4) == 0 && (H % 2) == 0 && (W % 2) == 0, "unpool2_bwd: bad arguments");
+    const int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 4);
+    hipLaunchKernelGGL(unpool2_bwd_kernel, dim3(ew_grid(total)), dim3(EW_BLOCK), 0, (hipStream_t)stream, gy.ptr, gy.ctot, gy.coff, map,
+                       gx.ptr, gx.ctot, gx.coff, N, H, W, C);
+    return tnr_check_launch("unpool2_bwd");
 }
 
 extern "C" int tnr_im2col(tnr_view x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad,

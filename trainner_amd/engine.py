@@ -73,6 +73,12 @@ class ConvOp:
         """This layer + nn.PixelShuffle(2) in one launch, y = the shuffled tensor (ops.conv_shuffle2); False: not available here."""
         return ops.conv_shuffle2(x, self.packer.get(self.i_f), y, layer=self.dirs[False][1], bias=self.mod.bias, **epi)
 
+    def fwd_pool2(self, x, y, route=None, **epi):
+        """This layer + its activation + nn.MaxPool2d(2, 2) in one launch, y = the pooled tensor (ops.conv_pool2); False: not available here."""
+        if self.mode_f != ops.CONV_3x3:
+            return False
+        return ops.conv_pool2(x, self.packer.get(self.i_f), y, route=route, layer=self.dirs[False][1], bias=self.mod.bias, **epi)
+
     def dgrad(self, g, gx, **epi):
         """gx = conv_transpose(g); for an UP2 layer gx lives in the up-sampled domain."""
         self._run(True, g, gx, epi)

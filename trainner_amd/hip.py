@@ -85,6 +85,8 @@ _SIGS = {
     "tnr_conv_wq_pack": (c_i, [C.POINTER(ConvDesc), c_p, c_l, c_p]),
     "tnr_conv_wino_bytes": (c_l, [C.POINTER(ConvDesc)]),
     "tnr_conv_wino_pack": (c_i, [C.POINTER(ConvDesc), c_p, c_l, c_p]),
+    "tnr_conv_pool_ok": (c_i, [C.POINTER(ConvDesc)]),
+    "tnr_conv_forward_pool2": (c_i, [C.POINTER(ConvDesc), c_p, c_p]),
     "tnr_gauss_mult": (c_i, [CView, CView, c_l, c_i, c_f, C.c_uint32, C.c_uint32, C.c_uint32, c_p]),
     "tnr_im2col": (c_i, [CView, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "tnr_conv_chain_workspace_bytes": (c_l, [C.POINTER(ConvDesc)]),
@@ -115,6 +117,7 @@ _SIGS = {
     "tnr_space_to_depth_bwd": (c_i, [CView, CView, c_i, c_i, c_i, c_i, CView, c_f, c_p]),
     "tnr_maxpool2_fwd": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_p]),
     "tnr_maxpool2_bwd": (c_i, [CView, CView, CView, c_i, c_i, c_i, c_i, c_p]),
+    "tnr_unpool2_bwd": (c_i, [CView, c_p, CView, c_i, c_i, c_i, c_i, c_p]),
     "tnr_gconv_fwd": (c_i, [CView, c_i, c_i, c_i, c_i, c_p, c_p, CView, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "tnr_gconv_dgrad": (c_i, [CView, c_i, c_i, c_i, c_i, c_p, CView, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "tnr_gconv_wgrad_workspace_bytes": (c_l, [c_i, c_i, c_i]),

@@ -59,6 +59,28 @@ def vgg_layer_names(net):
 TORCHVISION_FILES = {"vgg11": "vgg11-8a719046.pth", "vgg13": "vgg13-19584684.pth", "vgg16": "vgg16-397923af.pth", "vgg19": "vgg19-dcbb9e9d.pth"}
 
 
+class PooledAway:
+    """The tape's place-holder for the full-resolution activation of a conv + ReLU + pool triple that ran as one launch
+    (FeatureExtractor._fwd_pooled): the map was never stored; what is kept is the pooled map and one route byte per pooled element
+    (bits 0-1: the window position the pool picked, bit 2: pooled value > 0)."""
+    __slots__ = ("route", "pooled")
+
+    def __init__(self, route, pooled):
+        self.route, self.pooled = route, pooled
+
+    def dense(self):
+        """torch stand-in [N, H, W, C] for inspection (debug / tests only, like View.dense): the pooled value at the position the pool
+        picked, -inf at the three positions it did not -- their values do not exist.  `> 0` is the ReLU branch at every position a
+        gradient can reach, and F.max_pool2d(..., return_indices=True) finds the winners."""
+        p = self.pooled.dense()
+        N, Hp, Wp, Cc = p.shape
+        arg = self.route & 3
+        out = torch.full((N, Hp, 2, Wp, 2, Cc), float("-inf"), dtype=p.dtype, device=p.device)
+        for k in range(4):
+            out[:, :, k >> 1, :, k & 1] = torch.where(arg == k, p, out[:, :, k >> 1, :, k & 1])
+        return out.reshape(N, 2 * Hp, 2 * Wp, Cc)
+
+
 class FeatureExtractor(HipNet):
     def __init__(self, listen_list=None, net="vgg19", use_input_norm=True, z_norm=False, requires_grad=False,
                  remove_pooling=False, pooling_stride=2, change_padding=False, load_path=None, allow_random_init=False):
@@ -157,6 +179,37 @@ class FeatureExtractor(HipNet):
             self._norm = (scale, shift)
         return self._norm
 
+    def _fwd_pooled(self, i, cur, save):
+        """names[i] = convX_Y followed by reluX_Y and poolX with no tap on the conv or the relu: the three layers as ONE launch that
+        stores the pooled map only (ops.conv_pool2) -> the two tape entries (convX_Y, cur, away) and (poolX, away,
+        pooled view); away: a PooledAway in the place of the full-resolution map, with the arg-max / sign bytes the backward routes
+        by (None when nothing is saved: no full-resolution tensor and no bytes exist then).  None: not such a triple, or the launch
+        is declined -- nothing ran, the caller keeps its launches."""
+        names = self.names
+        n = names[i]
+        if (i + 2 >= len(names) or not names[i + 2].startswith("pool") or n in self.listen_list or names[i + 1] in self.listen_list
+                or not ops.pool_fold_on() or cur.H % 2 or cur.W % 2):
+            return None
+        shape = (cur.N, cur.H // 2, cur.W // 2, self.feature_net[n].out_channels)
+        dev = cur.buf.device
+        y = View(new_act(*shape, dev))
+        route = torch.empty(shape, dtype=torch.uint8, device=dev) if save else None
+        if not self._ops[n].fwd_pool2(cur, y, route=route, act=ops.ACT_RELU):
+            return None
+        away = PooledAway(route, y) if save else None
+        return [(n, cur, away), (names[i + 2], away, y)]
+
+    @staticmethod
+    def _pool_bwd(g, xin, y):
+        """Gradient of a pool's input (with ReLU' of the pooled activation) from the tape entry (poolX, xin, y): xin is the
+        full-resolution activation, or the PooledAway of a pooled convolution store."""
+        gx = View(new_act(y.N, 2 * y.H, 2 * y.W, y.C, y.buf.device))
+        if isinstance(xin, View):
+            ops.maxpool2_bwd(g, xin, gx)                                  # routes + ReLU' of the pooled activation
+        else:
+            ops.unpool2_bwd(g, xin.route, gx)                             # the same, from the bytes
+        return gx
+
     def engine_forward(self, x, save):
         N, Cc, H, W = x.shape
         if Cc != 3:
@@ -165,9 +218,14 @@ class FeatureExtractor(HipNet):
         scale, shift = self._norm_consts(dev)
         x4 = View(new_act(N, H, W, 4, dev))
         ops.nchw_to_nhwc(x, x4, Cpad=4, scale=scale, shift=shift)
-        cur, tape = x4, []
-        for n in self.names:
+        cur, tape, folded = x4, [], None
+        for i, n in enumerate(self.names):
             if n.startswith("conv"):
+                entries = self._fwd_pooled(i, cur, save)
+                if entries is not None:                                   # conv + ReLU + the pool behind them: one launch
+                    tape += entries
+                    cur, folded = entries[1][2], entries[1][0]
+                    continue
                 y = View(new_act(N, cur.H, cur.W, self.feature_net[n].out_channels, dev))
                 if n == self.listen:
                     self._ops[n].fwd(cur, y)                              # listened pre-ReLU
@@ -175,7 +233,7 @@ class FeatureExtractor(HipNet):
                     self._ops[n].fwd(cur, y, act=ops.ACT_RELU)
                 tape.append((n, cur, y))
                 cur = y
-            elif n.startswith("pool"):
+            elif n.startswith("pool") and n != folded:
                 y = View(new_act(N, cur.H // 2, cur.W // 2, cur.C, dev))
                 ops.maxpool2_fwd(cur, y)
                 tape.append((n, cur, y))
@@ -196,10 +254,10 @@ class FeatureExtractor(HipNet):
         g = View(g_nhwc)
         for i in range(len(tape) - 1, -1, -1):
             n, xin, y = tape[i]
-            gx = View(new_act(N, xin.H, xin.W, xin.C, dev))
             if n.startswith("pool"):
-                ops.maxpool2_bwd(g, xin, gx)                              # routes + ReLU' of the pooled activation
+                gx = self._pool_bwd(g, xin, y)
             else:
+                gx = View(new_act(N, xin.H, xin.W, xin.C, dev))
                 prev = tape[i - 1][0] if i > 0 else None
                 if prev is not None and prev.startswith("conv"):
                     self._ops[n].dgrad(g, gx, mask=xin, m_slope=0.0)      # ReLU' of the producing conv
@@ -222,9 +280,14 @@ class FeatureExtractor(HipNet):
         scale, shift = self._norm_consts(dev)
         x4 = View(new_act(N, H, W, 4, dev))
         ops.nchw_to_nhwc(x, x4, Cpad=4, scale=scale, shift=shift)
-        cur, tape, feats = x4, [], {}
+        cur, tape, feats, folded = x4, [], {}, None
         for i, n in enumerate(self.names):
             if n.startswith("conv"):
+                entries = self._fwd_pooled(i, cur, save)
+                if entries is not None:                                   # conv + ReLU + the pool behind them: one launch
+                    tape += entries
+                    cur, folded = entries[1][2], entries[1][0]
+                    continue
                 y = View(new_act(N, cur.H, cur.W, self.feature_net[n].out_channels, dev))
                 if n not in self.listen_list:
                     self._ops[n].fwd(cur, y, act=ops.ACT_RELU)
@@ -238,12 +301,13 @@ class FeatureExtractor(HipNet):
                 tape.append((n, cur, y))
                 cur = y
             elif n.startswith("pool"):
-                y = View(new_act(N, cur.H // 2, cur.W // 2, cur.C, dev))
-                ops.maxpool2_fwd(cur, y)
-                tape.append((n, cur, y))
-                cur = y
-                if n in self.listen_list:
-                    feats[n] = y
+                if n != folded:
+                    y = View(new_act(N, cur.H // 2, cur.W // 2, cur.C, dev))
+                    ops.maxpool2_fwd(cur, y)
+                    tape.append((n, cur, y))
+                    cur = y
+                if n in self.listen_list:                                 # (a folded pool's tap is the tensor the launch stored)
+                    feats[n] = cur
             elif n in self.listen_list:                                   # reluX_Y: the post-ReLU map the next layer reads
                 feats[n] = cur
         outs = tuple(feats[n].buf.permute(0, 3, 1, 2) for n in self.taps)
@@ -258,7 +322,9 @@ class FeatureExtractor(HipNet):
         """Add the tap gradients of `entry`'s output maps to the running gradient g (None: nothing arrived from above yet), in the
         running form: with respect to the PRE-activation map for a conv (the ReLU mask of the layer above already applied to what
         came through it), to the pooled map for a pool.  Tap gradients are never written to."""
-        n, _, y = entry
+        n, xin, y = entry
+        if not isinstance(y, View):                                       # a conv folded with its pool (_fwd_pooled): no tap listens on it
+            return g
         dev = y.buf.device
 
         def add(g, t):
@@ -291,10 +357,10 @@ class FeatureExtractor(HipNet):
         for i in range(len(tape) - 1, -1, -1):
             n, xin, y = tape[i]
             if g is not None:
-                gx = View(new_act(N, xin.H, xin.W, xin.C, dev))
                 if n.startswith("pool"):
-                    ops.maxpool2_bwd(g, xin, gx)                          # routes + ReLU' of the pooled activation
+                    gx = self._pool_bwd(g, xin, y)
                 else:
+                    gx = View(new_act(N, xin.H, xin.W, xin.C, dev))
                     prev = tape[i - 1][0] if i > 0 else None
                     if prev is not None and prev.startswith("conv"):
                         self._ops[n].dgrad(g, gx, mask=xin, m_slope=0.0)  # ReLU' of the producing conv

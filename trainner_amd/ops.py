@@ -525,6 +525,47 @@ def conv(x, wp, y, mode=CONV_3x3, wino=None, family=None, **epi):
 
 
 # ----------------------------------------------------------------------------------------------
+# conv + activation + nn.MaxPool2d(2, 2) in one launch: the pooled store of the Winograd form
+# ----------------------------------------------------------------------------------------------
+_NATIVE_CONV = conv             # (a test backend that replaces ops.conv has no pooled store: conv_pool2 then declines)
+_FullRes = collections.namedtuple("_FullRes", "N H W C pixels")          # what conv_plan reads of an output view that is never allocated
+
+
+def pool_fold_on():
+    """TNR_POOL_FOLD (default 1, read at call time; A/B switch): 0 keeps conv and maxpool2_fwd / maxpool2_bwd as launches of their own."""
+    return os.environ.get("TNR_POOL_FOLD", "1") != "0"
+
+
+def conv_pool2(x, wp, y, route=None, layer=None, wino=None, **epi):
+    """y [N, H / 2, W / 2, C] = maxpool2x2(act(conv3x3(x) + bias) * alpha) in ONE launch, bit for bit what conv + maxpool2_fwd store;
+    the [N, H, W, C] map does not exist (tnr_conv_forward_pool2).  route: None, or a uint8 tensor of y's shape that receives the
+    arg-max / sign bytes unpool2_bwd routes the gradient by.  An epilogue of the Winograd form: conv_plan's answers do not change.
+    Returns False, and launches nothing, unless the native library is the backend, TNR_POOL_FOLD is on, conv_plan says "wino" for
+    the unpooled launch (wino: as in conv) and the library agrees (tnr_conv_pool_ok): the caller then runs conv and maxpool2_fwd."""
+    if conv is not _NATIVE_CONV or not x.buf.is_cuda or not pool_fold_on() or x.H % 2 or x.W % 2 or (y.N, y.H, y.W) != (x.N, x.H // 2, x.W // 2):
+        return False
+    full = _FullRes(x.N, x.H, x.W, y.C, x.N * x.H * x.W)
+    if conv_plan(x, wp, full, CONV_3x3, epi, 0, layer, wino)[0] != "wino":
+        return False
+    lib, d = hip.load(), ConvDesc()
+    _conv_desc(d, x, wp, y, CONV_3x3, **epi)
+    d.Ho, d.Wo = x.H, x.W               # the descriptor of the UNPOOLED launch; only y is the pooled view
+    if not lib.tnr_conv_pool_ok(C.byref(d)):
+        return False
+    img = _wino_image(lib, d, wp, x.buf.device)
+    if img is None:
+        return False
+    d.wq, d.wq_bytes, d.wq_form = img.data_ptr(), img.numel() * 4, 1
+    if route is not None:
+        assert route.dtype == torch.uint8 and route.is_contiguous() and tuple(route.shape) == (y.N, y.H, y.W, y.C)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(lib.tnr_conv_forward_pool2(C.byref(d), hip.ptr(route), hip.stream()), "conv_forward_pool2")
+    if PROFILE is not None:             # (the convolution's own FLOP: the pooled store changes none of it)
+        PROFILE.end("conv_wino_3x3", 2.0 * d.N * d.Ho * d.Wo * 9 * min(x.C, wp.KinP) * d.Cout, t0, (x.C, d.Cout, d.Ho, wp.kind))
+    return True
+
+
+# ----------------------------------------------------------------------------------------------
 # nearest x2 + 3x3 (upconv_block) folded into the four-tap stride-2 launches
 # ----------------------------------------------------------------------------------------------
 UPFOLD_FAMILY = "conv_upfold"           # PROFILE family of the folded launches (all three passes), counted with the FLOP they execute (16 taps)
@@ -1128,6 +1169,13 @@ def maxpool2_fwd(x, y):
 
 def maxpool2_bwd(gy, x, gx):
     hip.check(hip.load().tnr_maxpool2_bwd(gy.c(), x.c(), gx.c(), x.N, x.H, x.W, x.C, hip.stream()), "maxpool2_bwd")
+
+
+def unpool2_bwd(gy, route, gx):
+    """maxpool2_bwd from the route bytes conv_pool2 wrote ([N, H / 2, W / 2, C] uint8) instead of the full-resolution activation."""
+    assert route.dtype == torch.uint8 and route.is_contiguous() and tuple(route.shape) == (gy.N, gy.H, gy.W, gy.C)
+    assert (gx.N, gx.H, gx.W, gx.C) == (gy.N, 2 * gy.H, 2 * gy.W, gy.C)
+    hip.check(hip.load().tnr_unpool2_bwd(gy.c(), route.data_ptr(), gx.c(), gx.N, gx.H, gx.W, gx.C, hip.stream()), "unpool2_bwd")
 
 
 def bilinear2x_fwd(x, y):
