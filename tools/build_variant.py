@@ -11,6 +11,7 @@ from trainner_amd import build as B  # noqa: E402
 
 
 def main(name, *defs):
+    assert not name.startswith("-"), "usage: build_variant.py NAME [-D...]: the first argument is the variant's name, not a flag"
     # --only a.hip,b.hip : recompile just these sources with the flags and link them with the SHIPPED build's other objects
     only = None
     defs = list(defs)

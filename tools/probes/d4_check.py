@@ -1,6 +1,6 @@
-"""conv3x3_d4_kernel (csrc/conv_sweep.hip: 64-cout 3x3 layers on the direct-sweep machinery, weights as a pre-split stream) against the
+"""conv3x3_d4_kernel (csrc/conv_sweep.hip: 64-cout 3x3 layers on the sweep machinery, weights as a pre-split stream) against the
 kernels it replaces (conv3x3_x3w8_kernel / conv_tile_kernel, ops.X3_D4 = False): bit equality over the benchmark's layer shapes with every
-epilogue form, then timing of both.    TNR_MMA=bf16x3 [TNR_D4_OCC=1|2] python tools/probes/d4_check.py [--time-only]"""
+epilogue form, then timing of both.    TNR_MMA=bf16x3 python tools/probes/d4_check.py [--time-only]"""
 import os
 import sys
 

@@ -41,9 +41,7 @@ if __name__ == "__main__":
         sys.exit(0)
     print("DIAG SLOW BOX: trying the other forms", flush=True)
     os.system("rocm-smi --showclocks --showpower 2>/dev/null | grep -E 'fclk|mclk|sclk|socclk|Power' | tr '\\n' ' '; echo")
-    for name, env in (("dma form", {"TNR_SWEEP_FORM": "dma"}), ("eight waves", {"TNR_SWEEP_WAVES": "8"}), ("dispensers per XCD", {"TNR_SWEEP_DISPENSERS": "8"}),
-                      ("chain kernel (x3)", {"TNR_CONV_SWEEP": "0"}), ("chain 8-wave x3", {"TNR_CONV_SWEEP": "0", "TNR_CHAIN_X3W8": "1"}),
-                      ("per layer", {"TNR_CONV_CHAIN": "0"}), ("fp32 mfma chain", {"TNR_MMA": "f32"}), ("default again", {})):
+    for name, env in (("chain kernel (x3)", {"TNR_CONV_SWEEP": "0"}), ("per layer", {"TNR_CONV_CHAIN": "0"}), ("fp32 mfma chain", {"TNR_MMA": "f32"}), ("default again", {})):
         e = dict(os.environ, DIAG_TAG=name, **env)
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one"], env=e, capture_output=True, text=True, timeout=300)
         print("\n".join(l for l in r.stdout.splitlines() if l.startswith("DIAG")) or ("DIAG %s FAILED: %s" % (name, r.stderr[-300:])), flush=True)

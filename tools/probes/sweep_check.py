@@ -139,8 +139,8 @@ def main():
     lib = hip.load()
     if hasattr(lib, "tnr_debug_sweep_timeline"):       # -DSW_TIMELINE probe build: where wave 0 of a workgroup spends its cycles
         import ctypes as C
-        names = ["tile prologue", "neighbour wait", "A load issue", "vmcnt wait", "barrier", "DMA issue", "MFMA bodies (four-wave form: whole chunks, incl. 2 syncs + side work)",
-                 "A split + LDS store", "epilogue", "  chunks with 3 N-tiles", "  chunks with 2 N-tiles", "  chunks with 1 N-tile", "", "", "kernel total", "slots"]
+        names = ["tile prologue", "neighbour wait", "A load issue", "", "chunk-top barrier", "", "MFMA bodies (whole chunks, incl. side work)",
+                 "", "epilogue", "  chunks with 3 N-tiles", "  chunks with 2 N-tiles", "  chunks with 1 N-tile", "", "", "kernel total", "chunks"]
         run = block(16, 128, 128, seed=5, grad_shape=False)
         _, _, st = run("layers")
         ops.conv_chain(st)
@@ -156,14 +156,14 @@ def main():
         torch.cuda.synchronize()
         lib.tnr_debug_sweep_timeline(out, 0)
         wgs = 256 * reps
-        print("sweep timeline: mean cycles per workgroup and launch (wave 0; 4 tiles per workgroup), %d slots" % (out[15] // wgs))
+        print("sweep timeline: mean cycles per workgroup and launch (wave 0; 4 tiles per workgroup), %d chunks" % (out[15] // wgs))
         for i, nm in enumerate(names):
-            if nm and nm != "slots":
+            if nm and nm != "chunks":
                 print("   %-40s %10.0f  (%5.1f %%)" % (nm, out[i] / wgs, 100.0 * out[i] / max(out[14], 1)))
         if hasattr(lib, "tnr_debug_sweep_units"):
             lib.tnr_debug_sweep_units(out2, 0)
-            print("four-wave form: mean cycles per unit (12 MFMAs = 384 cycles of matrix core) by unit class")
-        names2 = ["unit with the slot synchronisation", "first two units of a slot (weight DMA)", "units with an input-chunk item", "plain units"]
+            print("mean cycles per unit (12 MFMAs = 384 cycles of matrix core) by unit class")
+        names2 = ["", "", "units with an input-chunk item", "plain units"]
         for i in range(8):
             if out2[8 + i]:
                 print("   %d N-tiles: %-45s %8.0f   (%d units per workgroup and launch)" % (3 if i < 4 else 2, names2[i % 4], out2[i] / out2[8 + i], out2[8 + i] // wgs))

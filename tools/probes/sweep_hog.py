@@ -1,7 +1,7 @@
 """How do the dense-block sweep launches behave when NOT every CU is available?  A spinning one-workgroup kernel (tools/probes/cu_hog.hip: 100 KB
 of LDS, so no sweep workgroup fits next to it) holds `blocks` CUs on a side stream while tnr_conv_sweep runs; timing per launch with and without it,
-for the four-wave form (tiles dispensed from per-XCD counters) and the eight-wave form (static deal: needs the whole grid resident).
-    TNR_SWEEP_WAVES=4|8 python tools/probes/sweep_hog.py"""
+(tiles are dispensed in order from one counter, so the launch needs only a handful of resident workgroups to make progress).
+    python tools/probes/sweep_hog.py"""
 import ctypes as C
 import os
 import sys
@@ -43,9 +43,8 @@ def timed(blocks, reps=20):
     return 1e3 * e0.elapsed_time(e1) / reps
 
 
-print("TNR_SWEEP_WAVES=%s TNR_SWEEP_FORM=%s: per launch alone %.1f us; with 1 / 4 / 8 / 16 CUs held (what RCCL's ring kernels do to a launch next to them) "
-      "%.1f / %.1f / %.1f / %.1f us; error flag %d" % (os.environ.get("TNR_SWEEP_WAVES", "4"), os.environ.get("TNR_SWEEP_FORM", "direct"), timed(0), timed(1), timed(4),
-                                                      timed(8), timed(16), ops.chain_error_flag()))
+print("per launch alone %.1f us; with 1 / 4 / 8 / 16 CUs held (what RCCL's ring kernels do to a launch next to them) "
+      "%.1f / %.1f / %.1f / %.1f us; error flag %d" % (timed(0), timed(1), timed(4), timed(8), timed(16), ops.chain_error_flag()))
 # and the results do not depend on who else is on the chip: bit-identical with 16 CUs held
 ref_buf, ref_out, _ = run("sweep")
 hog.cu_hog(C.c_void_p(side.cuda_stream), 60.0, C.c_void_p(out.data_ptr()), 16)

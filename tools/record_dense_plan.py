@@ -32,11 +32,9 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "dense_plan.json")
 NF, GC, CUS = 64, 32, 4
 KINDS = ("train", "grad", "chain3", "ineligible", "big_grid", "unsweepable")
 MMAS = {"f32": hip.MMA_F32, "bf16": hip.MMA_BF16, "bf16x3": hip.MMA_BF16X3}
-DEFAULTS = dict(CONV_CHAIN=True, CONV_SWEEP=True, CHAIN_X3=True, AMP_SWEEP=True, SWEEP_DISPENSED=True, SWEEP_AUTO=True, DENSE_SPLIT=True,
-                _SWEEP_FORM_DMA=False, CHAIN_WITH_COLLECTIVES=False)
+DEFAULTS = dict(CONV_CHAIN=True, CONV_SWEEP=True, CHAIN_X3=True, AMP_SWEEP=True, SWEEP_AUTO=True, DENSE_SPLIT=True, CHAIN_WITH_COLLECTIVES=False)
 # every switch alone against the defaults, then the pairs that interact (buckets-in-flight is a dimension of its own below)
-FLIPS = [()] + [(k,) for k in DEFAULTS] + [("CONV_SWEEP", "AMP_SWEEP"), ("DENSE_SPLIT", "_SWEEP_FORM_DMA"), ("CHAIN_WITH_COLLECTIVES", "CONV_CHAIN"),
-                                           ("SWEEP_DISPENSED", "CHAIN_WITH_COLLECTIVES")]
+FLIPS = [()] + [(k,) for k in DEFAULTS] + [("CONV_SWEEP", "AMP_SWEEP"), ("CHAIN_WITH_COLLECTIVES", "CONV_CHAIN")]
 CHOICES = (None, "sweep", "layers")
 STATES = list(itertools.product(CHOICES, (False, True), (False, True)))      # (choice, buckets in flight, on device)
 
@@ -114,14 +112,14 @@ def stages(ops, kind, on_device):
 @contextlib.contextmanager
 def stand_ins(ops, lib):
     saved_hip = (hip.load, hip.stream)
-    names = list(DEFAULTS) + ["MMA", "FP32_MMA", "COLLECTIVES_IN_FLIGHT", "PROFILE", "SWEEP_PACK_BATCH", "conv", "_cus", "_FAULT"]
+    names = list(DEFAULTS) + ["MMA", "FP32_MMA", "COLLECTIVES_IN_FLIGHT", "PROFILE", "conv", "_cus", "_FAULT"]
     saved = {k: getattr(ops, k) for k in names}
     state = dict(ops.SWEEP_AUTO_STATE)
     counters = dict(ops.COUNTERS)
     hip.load, hip.stream = (lambda *a, **k: lib), (lambda: 0)
     ops.conv = lambda *a, **k: lib.calls.append(("conv", k.get("wino")))
     ops._cus = lambda dev: CUS
-    ops.PROFILE, ops.SWEEP_PACK_BATCH, ops._FAULT = None, False, None
+    ops.PROFILE, ops._FAULT = None, None
     try:
         yield
     finally:

@@ -1,5 +1,5 @@
 // The quad-transpose epilogue of conv_body.h as a function (same arithmetic, same order), for the kernels that do not go through
-// conv_tile_body: conv_x3w8.h and the LDS-DMA experiments (conv_body_dl.h).
+// conv_tile_body: conv_x3w8.h.
 #pragma once
 #include "conv_body.h"
 

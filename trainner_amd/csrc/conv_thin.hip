@@ -351,8 +351,7 @@ extern "C" int tnr_conv_thin7(tnr_view x, int32_t N, int32_t H, int32_t W, int32
     k.tiles_x = tnr_cdiv(Wo, T7); k.tiles_y = tnr_cdiv(Ho, T7);
     const int64_t tiles = (int64_t)k.tiles_x * k.tiles_y * N;
     TNR_REQUIRE(tiles < (1LL << 31), "conv_thin7: grid too large");
-    static const bool lanes_c = [] { const char *e = std::getenv("TNR_THIN7_LANES"); return e == nullptr || e[0] != 'p'; }();      // p: lanes = pixels (A/B switch)
-    if (lanes_c && Cin <= 64 && Cout <= 3) {      // (a lane keeps 49 x 3 weights: a 4-channel output takes the lanes = pixels kernel below)
+    if (Cin <= 64 && Cout <= 3) {      // (a lane keeps 49 x 3 weights: a 4-channel output takes the lanes = pixels kernel below)
         const int nseg = tnr_cdiv(Wo, T7C_SEG), seg = tnr_cdiv(Wo, nseg);
         const int64_t waves = (int64_t)N * tnr_cdiv(Ho, 2) * nseg;
         TNR_REQUIRE(waves < (1LL << 31), "conv_thin7: grid too large");

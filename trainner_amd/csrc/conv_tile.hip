@@ -21,9 +21,6 @@
 #include "conv_body.h"
 #include "conv_x3w8.h"
 #include <cstdlib>
-#ifdef TNR_CONV_DL_EXPERIMENT     /* tools/build_variant.py dl -DTNR_CONV_DL_EXPERIMENT: the LDS-DMA staging experiments, conv_body_dl.h */
-#include "conv_body_dl.h"
-#endif
 
 namespace {
 
@@ -253,17 +250,6 @@ extern "C" int tnr_conv_forward(const tnr_conv_desc *d, void *stream) {
         static const bool w8 = [] { const char *e = std::getenv("TNR_X3_W8"); return e == nullptr || e[0] != '0'; }();
         if (w8 && d->mode == TNR_CONV_3x3 && nt == 2 && tw == 32 && sh >= 16 && conv3x3_x3w8_ok(k)) return launch_conv3x3_x3w8(k, s);
     }
-#ifdef TNR_CONV_DL_EXPERIMENT
-    const char *dl_env = std::getenv("TNR_CONV_DL");     // (experiment switch, read per call so that one process can compare both paths)
-    const int dl = dl_env != nullptr ? dl_env[0] - '0' : 0;      // 1: 8-wave / 16-channel form, 2: 4-wave / 8-channel form
-    if (dl == 1 && d->mode == TNR_CONV_3x3 && nt == 2 && tw == 32 && sh >= 16 && conv3x3_dl_ok(k)) return launch_conv3x3_dl<0>(k, s);
-    if (dl == 4 && d->mode == TNR_CONV_3x3 && nt == 2 && tw == 32 && sh >= 16 && conv3x3_dl_ok(k)) return launch_conv3x3_dl<2>(k, s);     // 4: form 1 with two loader waves
-    if (dl == 5 && d->mode == TNR_CONV_3x3 && nt == 2 && tw == 32 && sh >= 16 && conv3x3_dl_ok(k)) return launch_conv3x3_dl<4>(k, s);     // 5: four loader waves
-    if (dl == 2 && d->mode == TNR_CONV_3x3 && tw == 32 && conv3x3_dl_ok(k)) {
-        if (big_m) return launch_conv3x3_dk8<1, 4>(k, tiles, s);
-        if (nt == 2) return launch_conv3x3_dk8<2, 2>(k, tiles, s);
-    }
-#endif
     if (big_m) {
         rc = launch_conv<TNR_CONV_3x3, 32, 1, 4>(k, (int)tiles, s);
     } else {

@@ -118,7 +118,6 @@ class WeightPacker:
 
     def _finalize(self):
         self.__dict__.pop("_sweep_images", None)       # derived layouts of the old slabs
-        self.__dict__.pop("_sweep_batch", None)
         self.__dict__.pop("_wq_images", None)
         total = sum(round_up(j[4], 64) for j in self.jobs)
         self.flat = torch.empty(total, dtype=torch.float32, device=self.device)
@@ -148,7 +147,6 @@ class WeightPacker:
         hip.check(hip.load().tnr_pack_weights(self.table.data_ptr(), len(self.jobs), self.max_out, hip.stream()),
                   "pack_weights")
         self.gen += 1
-        _repack_sweep_images(self)
 
 
 class DensePacker:
@@ -178,7 +176,6 @@ class DensePacker:
 
     def _finalize(self):
         self.__dict__.pop("_sweep_images", None)
-        self.__dict__.pop("_sweep_batch", None)
         self.__dict__.pop("_wq_images", None)          # (dense_block: the transform-domain stream of the mirror's last stage)
         total = sum(round_up(j[7], 64) for j in self.jobs)
         self.flat = torch.empty(total, dtype=torch.float32, device=self.device)
@@ -210,7 +207,6 @@ class DensePacker:
         hip.check(hip.load().tnr_pack_dense_dgrad(self.table.data_ptr(), len(self.jobs), self.max_out, hip.stream()),
                   "pack_dense_dgrad")
         self.gen += 1
-        _repack_sweep_images(self)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -652,7 +648,6 @@ CONV_CHAIN = os.environ.get("TNR_CONV_CHAIN", "1") != "0"     # 0: one launch pe
 CONV_SWEEP = os.environ.get("TNR_CONV_SWEEP", "1") != "0"     # 0: tnr_conv_chain where tnr_conv_sweep would run
 CHAIN_X3 = os.environ.get("TNR_CHAIN_X3", "1") == "1"   # 0: TNR_MMA=bf16x3 launches demote to the fp32 matrix core inside tnr_conv_chain
 AMP_SWEEP = os.environ.get("TNR_AMP_SWEEP", "1") != "0"      # 0: use_amp (bf16 operands) keeps tnr_conv_chain instead of the sweep's bf16-operand form
-SWEEP_DISPENSED = os.environ.get("TNR_SWEEP_WAVES", "4") != "8"      # the four-wave forms take their tiles from an atomic counter (conv_sweep.hip)
 # TNR_CHAIN_WITH_COLLECTIVES=1: keep the one-launch forms while gradient buckets are on the wire.  Measured next to a 4 x 64 MB RCCL
 # all-reduce on a side stream (1-rank group, tools/chain_stress.py --rccl, profiles/r03j): bit-identical results, no wait ever timed out,
 # +0.10 ms per dense-block launch (sweep 0.61 -> 0.71 ms, chain 1.01 -> 1.14 ms).  Off by default: with N > 1 ranks an RCCL kernel waits
@@ -673,7 +668,6 @@ SWEEP_AUTO_STATE = {"choice": None, "sweep_us": None, "layers_us": None}     # c
 # form's error (<= 3 x the fp32 matrix core's against fp64, as everywhere that form runs) and is deterministic.  The five-stage sweep's time is
 # set by the matrix core's dynamic energy, so the instructions removed are what pays.  Measured: DESIGN.md 3.2.
 DENSE_SPLIT = os.environ.get("TNR_DENSE_SPLIT", "1") != "0"
-_SWEEP_FORM_DMA = os.environ.get("TNR_SWEEP_FORM", "")[:2] == "dm"      # (the four-stage plan exists in the direct four-wave form only)
 COLLECTIVES_IN_FLIGHT = False   # True (dp.py) from the first gradient bucket handed to RCCL on the side stream until the compute stream has waited for all
 COUNTERS = {"one_launch_next_to_collectives": 0, "per_layer_next_to_collectives": 0}      # dense blocks launched while gradient buckets were in flight
 _cu_counts = {}
@@ -718,14 +712,14 @@ def dense_block_plan(stages, crowded=_LIVE, mma=_LIVE, choice=_LIVE, sweepable=T
                        "calibrated": the calibration (this box's or another rank's) chose per-layer launches -- heeded where the sweep would run, in
                        the bf16x3 arithmetic, on the device, unless TNR_SWEEP_AUTO=0.  "crowded": gradient buckets are on the wire (unless
                        TNR_CHAIN_WITH_COLLECTIVES=1) and the form that would run needs its whole grid co-resident, which RCCL's kernels on the same
-                       CUs could delay: tnr_conv_chain and the eight-wave sweep.  The four-wave sweep DISPENSES its tiles in order (a waited-for tile
+                       CUs could delay: tnr_conv_chain.  The sweep DISPENSES its tiles in order (a waited-for tile
                        was either taken by a running workgroup or is the next to be dispensed): stage s of tile T reads stage s - 1 of T + tiles_x + 1,
                        so 4 (tiles_x + 1) + 1 resident workgroups guarantee progress (21 on the 128-wide trunk, never more than one image's tiles).
       ("chain", None)  tnr_conv_chain: every eligible list the sweep does not exist for.
       ("sweep", None)  tnr_conv_sweep: five stages in the bf16x3 arithmetic (unless TNR_CHAIN_X3=0) or under bf16 operands (unless TNR_AMP_SWEEP=0),
                        four stages in bf16x3 (a split block's first four); TNR_CONV_SWEEP=0: never.
       ("split", None)  dense_block only (conv_chain reads it as "sweep"): the four-stage sweep, then the last stage as a Winograd launch.  Five stages of
-                       the dispensed bf16x3 sweep on the device, nothing crowded, _split_shape, unless TNR_DENSE_SPLIT=0 or the sweep's DMA form is selected.
+                       the bf16x3 sweep on the device, nothing crowded, _split_shape, unless TNR_DENSE_SPLIT=0.
     Everything is read at call time; the keyword arguments ask a what-if instead: crowded = buckets in flight, mma = the arithmetic, choice = the
     calibrated form, sweepable=False = tnr_conv_sweep declined this block; stages None = a well-shaped five-stage block on the device."""
     n = 5 if stages is None else len(stages)
@@ -740,12 +734,11 @@ def dense_block_plan(stages, crowded=_LIVE, mma=_LIVE, choice=_LIVE, sweepable=T
     if sweep and x3 and on_device and SWEEP_AUTO and (SWEEP_AUTO_STATE["choice"] if choice is _LIVE else choice) == "layers":
         return "layers", "calibrated"
     crowded = _crowded(COLLECTIVES_IN_FLIGHT if crowded is _LIVE else crowded)
-    dispensed = sweep and SWEEP_DISPENSED
-    if crowded and not dispensed:
+    if crowded and not sweep:
         return "layers", "crowded"
     if not sweep:
         return "chain", None
-    if DENSE_SPLIT and dispensed and x3 and n == 5 and on_device and not crowded and not _SWEEP_FORM_DMA and stages is not None and _split_shape(stages):
+    if DENSE_SPLIT and x3 and n == 5 and on_device and not crowded and stages is not None and _split_shape(stages):
         return "split", None
     return "sweep", None
 
@@ -772,27 +765,6 @@ def g_buckets_leave_in_backward():
     return want == "1" or (want == "auto" and dense_blocks_overlap_collectives())
 
 
-# every dense block's sweep image rebuilt in ONE launch per packer run (tnr_conv_sweep_pack_batch: 2 launches per optimiser step instead of 138).
-# OFF by default: measured 0.6-2.1 ms per step SLOWER than the per-block 5 us launches, which sit in launch gaps the stream pays anyway
-# (profiles/r10g_sweep_pack_batch_ab.txt); bit-identical either way.
-SWEEP_PACK_BATCH = os.environ.get("TNR_SWEEP_PACK_BATCH", "0") != "0"
-
-
-def _repack_sweep_images(owner):
-    """After `owner` (a WeightPacker / DensePacker) re-packed its weights: rebuild the sweep images of ALL its dense blocks in one launch
-    (tnr_conv_sweep_pack_batch) instead of one small launch per block at its first use -- 2 launches per optimiser step instead of
-    2 x 69 for RRDBNet-23.  The batch is the set of images _sweep_image has built for this owner so far."""
-    b = owner.__dict__.get("_sweep_batch")
-    if not b or not SWEEP_PACK_BATCH:
-        return
-    if b["table"] is None:
-        raw = b"".join(bytes(it) for it in b["items"])
-        b["table"] = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(b["ents"][0][0].device)
-    hip.check(hip.load().tnr_conv_sweep_pack_batch(b["table"].data_ptr(), len(b["items"]), b["max_units"], hip.stream()), "conv_sweep_pack_batch")
-    for ent in b["ents"]:
-        ent[1] = owner.gen
-
-
 _chain_epoch = {}
 
 
@@ -802,17 +774,8 @@ def _sweep_image(lib, descs, n, stages, dev):
     if need <= 0:
         return None
     owner = stages[0]["wp"].owner if all(st["wp"].owner is stages[0]["wp"].owner for st in stages) else None
-    ent, fresh = _stream_image(owner, "_sweep_images", tuple(st["wp"].t.data_ptr() for st in stages), need, dev,
+    ent, _ = _stream_image(owner, "_sweep_images", tuple(st["wp"].t.data_ptr() for st in stages), need, dev,
                                lambda img, nb: hip.check(lib.tnr_conv_sweep_pack(descs, n, img, nb, hip.stream()), "conv_sweep_pack"))
-    if fresh and owner is not None and SWEEP_PACK_BATCH:
-        # first build of this block's image: from the owner's next run() on it is rebuilt with all the others in one launch
-        item = hip.SweepPackItem()
-        hip.check(lib.tnr_conv_sweep_pack_item(descs, n, ent[0].data_ptr(), need, C.byref(item)), "conv_sweep_pack_item")
-        b = owner.__dict__.setdefault("_sweep_batch", {"items": [], "ents": [], "table": None, "max_units": 0})
-        b["items"].append(item)
-        b["ents"].append(ent)
-        b["table"] = None
-        b["max_units"] = max(b["max_units"], item.units)
     return ent[0]
 
 
