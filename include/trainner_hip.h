@@ -799,6 +799,21 @@ int tnr_ranger_step_guarded(float *p, const float *g, float *m, float *v, float 
                             const int64_t *segs, int32_t nseg, const int32_t *rowseg, int64_t nrows, void *ws, int64_t ws_bytes,
                             int32_t gc_min_dim, double b1, double b2, float eps, float weight_decay, float step, int32_t rectified,
                             int32_t lookahead, float alpha, const uint32_t *fault, void *stream);
+/* --- spectral normalisation of convolution weights (csrc/spectral_norm.hip; torch.nn.utils.spectral_norm, one power iteration, dim 0) ---
+ * jobs [njobs][tnr_sn_job_words()] int64, one row per wrapped layer: w, wn, u, v, ru, rv, sig, g, dw (device addresses), rows, K,
+ * tpart (double [ceil(rows / 16)][K]), s (float [rows]), gpart (double [ngpart]), ngpart, sspart (double [ceil(K / 256)]).  w is the [rows][K] parameter, wn the derived
+ * weight w / sigma, u / v the power-iteration vectors, ru / rv / sig the forward's record (the u, v, sigma that wn was made with), g the
+ * gradient with respect to wn and dw the parameter's gradient.  Tile tables, int32 [n][4]: wt_tiles = {job, first row (16 per tile),
+ * first column (1024 per tile), row-block index}; col_tiles = {job, first column (256 per tile), 0, index of the tile inside its job};
+ * row_tiles = {job, first row (4 per tile), 0, 0}; chunks = {job, first element (4096 per
+ * chunk), 0, index of the chunk inside its job}.
+ * tnr_sn_forward: iterate != 0 (training) v <- normalize(w^T u), u <- normalize(w v) in place, sigma = u . (w v), wn = w / sigma: 4
+ * launches; iterate == 0 (eval) sigma from the stored u and v, wn = w / sigma: 2 launches.  Both fill the record.
+ * tnr_sn_backward: dw += (g - <g, wn> ru rv^T) / sig: 2 launches.  Sums are fp64 in a fixed order; no atomics. */
+int32_t tnr_sn_job_words(void);
+int tnr_sn_forward(const int64_t *jobs, int32_t njobs, const int32_t *wt_tiles, int32_t n_wt, const int32_t *col_tiles, int32_t n_col,
+                   const int32_t *row_tiles, int32_t n_row, const int32_t *chunks, int32_t nchunks, int32_t iterate, float eps, void *stream);
+int tnr_sn_backward(const int64_t *jobs, int32_t njobs, const int32_t *chunks, int32_t nchunks, void *stream);
 /* Register ONE caller-owned, zero-initialised device word per process (one process drives one GPU) as the engine's fault latch:
  * the one-launch dense-block kernels (tnr_conv_chain, tnr_conv_sweep) set it to 1 when a bounded wait for a neighbouring tile gives
  * up (instead of the last word of their own workspace, which they use while no latch is registered).  Sticky: nothing in the

@@ -5,7 +5,7 @@ hand-written forward / backward kernel schedules of a whole network as ONE autog
 import torch
 
 from . import hip, ops
-from .flat import FlatParams
+from .flat import ALIGN, FlatParams
 
 
 class ConvOp:
@@ -136,6 +136,70 @@ class ConvOp:
         ops.wgrad_group([self.wgrad_item(x, g, alpha, cin_begin, with_bias)], mode=self.mode_f)
 
 
+class SpectralNormState:
+    """The spectrally normalised convolutions of one network (block.SpectralNormConv2dHIP) and their weight generations.
+
+    `derived` holds, per layer, the normalised weight W / sigma that the packer and the convolution kernels read, followed by the record
+    of the forward that made it (its u, v and sigma); `gws` is the workspace the weight-gradient kernels write dL/d(W / sigma) into.
+    Every training-mode forward makes a new generation (one power iteration); a forward that will be differentiated keeps a copy of
+    `derived`, and its backward puts that copy back first when a later forward has replaced it."""
+
+    def __init__(self, mods, device):
+        self.mods = list(mods)
+        al = lambda n: (n + ALIGN - 1) // ALIGN * ALIGN
+        offs, off, goff = [], 0, 0
+        for m in self.mods:
+            w = m.weight_orig
+            rows, n = w.shape[0], w.numel()
+            offs.append((off, off + al(n), off + al(n) + al(rows), off + al(n) + al(rows) + al(n // rows), goff))
+            off, goff = off + al(n) + al(rows) + al(n // rows) + ALIGN, goff + al(n)
+        self.derived = torch.zeros(off, dtype=torch.float32, device=device)
+        self.gws = torch.zeros(goff, dtype=torch.float32, device=device)
+        layers = []
+        for m, (o_w, o_u, o_v, o_s, o_g) in zip(self.mods, offs):
+            w = m.weight_orig
+            rows, n = w.shape[0], w.numel()
+            if m.weight_u.device != w.device or m.weight_v.device != w.device or w.device != self.derived.device:
+                raise hip.HipEngineError("spectral norm: weight_orig, weight_u and weight_v must live on the engine's device")
+            wn, g = self.derived[o_w:o_w + n].view(w.shape), self.gws[o_g:o_g + n].view(w.shape)
+            m.bind_derived(wn, g)
+            layers.append(dict(w=w, wn=wn, u=m.weight_u, v=m.weight_v, ru=self.derived[o_u:o_u + rows], rv=self.derived[o_v:o_v + n // rows],
+                               sig=self.derived[o_s:o_s + 1], g=g, dw=w.grad))
+        self.table = ops.SpectralNormTable(layers, device)
+        self.gen, self._count, self._snap = None, 0, None
+
+    def bound_to(self, mods):
+        """Still describing these modules' tensors (module.to() / load_state_dict(assign=True) replace buffers)?"""
+        mods = list(mods)
+        return len(mods) == len(self.mods) and all(
+            a is b and L["u"] is a.weight_u and L["v"] is a.weight_v and L["w"] is a.weight_orig and L["dw"].data_ptr() == a.weight_orig.grad.data_ptr()
+            for a, b, L in zip(mods, self.mods, self.table.layers))
+
+    def derive(self, iterate):
+        ops.sn_forward(self.table, iterate, eps=self.mods[0].eps)
+        self._count += 1
+        self.gen = self._count
+
+    def snapshot(self):
+        if self._snap is None or self._snap[0] != self.gen:
+            self._snap = (self.gen, self.derived.clone())
+        return self._snap
+
+    def restore(self, snap):
+        """-> True when the live generation was replaced (the caller re-packs)."""
+        if snap[0] == self.gen:
+            return False
+        self.derived.copy_(snap[1])
+        self.gen = snap[0]
+        return True
+
+    def begin_backward(self):
+        ops.fill(self.gws, 0.0)
+
+    def finish_backward(self):
+        ops.sn_backward(self.table)
+
+
 class _NetFn(torch.autograd.Function):
     """Whole-network autograd node.  Parameters are listed as inputs only so that autograd knows the
     output depends on them; their gradients are accumulated by the engine straight into the flat
@@ -146,7 +210,8 @@ class _NetFn(torch.autograd.Function):
         # (grad mode is always off inside Function.forward; needs_input_grad already accounts for it)
         need_param_grad = any(ctx.needs_input_grad[2:])
         need_graph = ctx.needs_input_grad[1] or need_param_grad
-        memo = net._memo_lookup(x) if (net.memoize and net.training) else None
+        memoize = net.memoize and not net._has_sn        # a spectrally normalised net's repeated forward is not a repeat
+        memo = net._memo_lookup(x) if (memoize and net.training) else None
         if memo is not None and memo[1] is not None:
             # same input values, same parameters as an earlier forward of this step: its output and saved activations ARE this
             # forward's; only the side effects of running it again (BatchNorm running statistics) are replayed
@@ -154,10 +219,11 @@ class _NetFn(torch.autograd.Function):
             net.replay_forward_side_effects(saved)
             out = out.detach()
         else:
-            out, saved = net.engine_forward(x, save=need_graph or (net.memoize and net.training))
-            if net.memoize and net.training:
+            out, saved = net.engine_forward(x, save=need_graph or (memoize and net.training))
+            if memoize and net.training:
                 net._memo_store(x, out, saved)
         ctx.net, ctx.saved, ctx.need_param_grad = net, (saved if need_graph else None), need_param_grad
+        ctx.sn_gen = net._sn.snapshot() if (need_graph and net._sn is not None) else None
         return out
 
     @staticmethod
@@ -169,8 +235,16 @@ class _NetFn(torch.autograd.Function):
         sched = getattr(ctx.net, "_bucket_schedule", None)
         if sched is not None and ctx.need_param_grad:
             sched.begin_pass()                      # dp.BucketSchedule: buckets leave in the last accumulating pass
+        sn = ctx.net._sn if ctx.sn_gen is not None else None
+        if sn is not None:
+            ctx.net._sn_restore(ctx.sn_gen)         # the weights, u, v and sigma of THIS forward
+            ctx.sn_gen = None
+            if ctx.need_param_grad:
+                sn.begin_backward()
         gx = ctx.net.engine_backward(saved, gout, need_input_grad=ctx.needs_input_grad[1],
                                      need_param_grad=ctx.need_param_grad)
+        if sn is not None and ctx.need_param_grad:
+            sn.finish_backward()
         return (None, gx) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
@@ -182,7 +256,8 @@ class HipNet(torch.nn.Module):
     # output and saved activations are shared, backward passes only read them.  SRModel.optimize_parameters shows the
     # discriminator the real batch and the generated batch twice between two discriminator updates (generator stage, then
     # discriminator stage on `fake.detach()`): 2 of its 4 forward passes per step are such repeats.  Entries hold a reference
-    # to their input (its address cannot be recycled while the entry lives) and die with the parameter version.
+    # to their input (its address cannot be recycled while the entry lives) and die with the parameter version.  A net with spectrally
+    # normalised layers never memoises, whatever is set here: its second forward has done one more power iteration.
     memoize = False
 
     def _memo_key(self, x):
@@ -212,12 +287,14 @@ class HipNet(torch.nn.Module):
 
     def _init_engine(self):
         self._memo, self._memo_ver = {}, None
+        self._has_sn = any(getattr(m, "spectral_norm", False) for m in self.modules())
         self._flat = FlatParams(self)
         self._packer = None
         self._dense_packer = None
         self._packer_owner = None
         self._packed_version = None
         self._ops = None
+        self._sn = None
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._flat.touch())
 
     def flat_params(self):
@@ -234,7 +311,11 @@ class HipNet(torch.nn.Module):
         fp = self.flat_params()
         if fp.flat.device != x.device:
             raise hip.HipEngineError("network is on %s but input on %s" % (fp.flat.device, x.device))
-        if self._packer is None or self._packer.device != x.device or self._packer_owner is not fp.flat:
+        sn_mods = [m for m in self.modules() if getattr(m, "spectral_norm", False)] if self._has_sn else []
+        if self._packer is None or self._packer.device != x.device or self._packer_owner is not fp.flat or \
+                (sn_mods and not self._sn.bound_to(sn_mods)):
+            # (the derived weights are bound before _build_ops hands `mod.weight` to the packer)
+            self._sn = SpectralNormState(sn_mods, x.device) if sn_mods else None
             self._packer = ops.WeightPacker(x.device)
             self._dense_packer = ops.DensePacker(x.device)
             self._packer_owner = fp.flat
@@ -244,11 +325,24 @@ class HipNet(torch.nn.Module):
         # fp.version: the D (4 forwards per step) and the frozen VGG are not re-packed needlessly
         # (fp.flat._version also moves on any in-place torch write through a parameter view)
         key = (fp.version, fp.flat._version)
+        if self._sn is not None and (self.training or self._packed_version != key):
+            # a new weight generation: one power iteration per training-mode forward (under no_grad too); in eval mode sigma from the
+            # stored u and v, when the parameters moved or a backward put an older generation back
+            self._sn.derive(iterate=self.training)
+            self._packed_version = None
         if self._packed_version != key:
             self._refresh_derived()
             self._packer.run()
             self._dense_packer.run()
             self._packed_version = key
+
+    def _sn_restore(self, snap):
+        """Put a saved forward's weight generation back (its W / sigma, u, v, sigma) and re-pack, unless it is the live one."""
+        if self._sn.restore(snap):
+            self._refresh_derived()
+            self._packer.run()
+            self._dense_packer.run()
+            self._packed_version = None         # an eval-mode forward re-derives before it runs
 
     def forward(self, x, **kw):
         x = x.contiguous()

@@ -48,6 +48,54 @@ class Conv2dHIP(nn.Module):
         return "%d, %d, k=%d, s=%d" % (self.in_channels, self.out_channels, self.kernel_size, self.stride)
 
 
+class SpectralNormConv2dHIP(nn.Module):
+    """A convolution under torch.nn.utils.spectral_norm (block.add_spectral_norm, block.py:136-141: hook form, one power iteration,
+    eps 1e-12, dim 0).  Holds what the reference's wrapped nn.Conv2d holds: the parameter `weight_orig`, the buffers `weight_u` [Cout]
+    and `weight_v` [Cin kh kw], `bias` where the layer has one, and NO `weight` key.  `weight` is the derived tensor W / sigma that the
+    network's engine rewrites (csrc/spectral_norm.hip) and every convolution kernel reads; its `.grad` is the workspace the weight-gradient
+    kernels write.  Until an engine binds it, `weight` aliases weight_orig's storage as the reference's attribute does after
+    construction: networks.init_weights, which selects this class by the 'Conv' in its name and writes into `m.weight`, therefore
+    initialises weight_orig here as there.  Construction draws, in order: weight, bias, u ~ N(0, 1), v ~ N(0, 1)."""
+
+    spectral_norm = True
+    eps = 1e-12
+
+    def __init__(self, in_nc, out_nc, kernel_size=3, stride=1, bias=True):
+        super().__init__()
+        self._derived = None
+        self.in_channels, self.out_channels = in_nc, out_nc
+        self.kernel_size, self.stride = kernel_size, stride
+        w = nn.Parameter(torch.empty(out_nc, in_nc, kernel_size, kernel_size))
+        b = nn.Parameter(torch.empty(out_nc)) if bias else None
+        nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+        if bias:
+            bound = 1.0 / math.sqrt(in_nc * kernel_size * kernel_size)
+            nn.init.uniform_(b, -bound, bound)
+        self.bias = b              # (the reference re-registers the weight behind the bias: state_dict order bias, weight_orig, u, v)
+        self.weight_orig = w
+        with torch.no_grad():
+            u = nn.functional.normalize(w.new_empty(out_nc).normal_(0, 1), dim=0, eps=self.eps)
+            v = nn.functional.normalize(w.new_empty(in_nc * kernel_size * kernel_size).normal_(0, 1), dim=0, eps=self.eps)
+        self.register_buffer("weight_u", u)
+        self.register_buffer("weight_v", v)
+
+    def forward(self, x):
+        raise RuntimeError("SpectralNormConv2dHIP is executed by its owning network's HIP engine, not called directly")
+
+    def extra_repr(self):
+        return "%d, %d, k=%d, s=%d, spectral norm" % (self.in_channels, self.out_channels, self.kernel_size, self.stride)
+
+    @property
+    def weight(self):
+        return self._derived if self._derived is not None else self.weight_orig.data
+
+    def bind_derived(self, wn, g):
+        """wn: the engine's [Cout, Cin, kh, kw] view for W / sigma; g: the same-shaped weight-gradient workspace.  None unbinds."""
+        if wn is not None:
+            wn.grad = g
+        self._derived = wn
+
+
 class Marker(nn.Module):
     """Parameter-free place holder that keeps nn.Sequential indices equal to the reference's
     (activation, Upsample, PixelShuffle positions)."""

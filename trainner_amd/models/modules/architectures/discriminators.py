@@ -153,8 +153,8 @@ class UNetDiscriminator(HipNet):
     Constructor, state_dict keys (conv0 .. conv9; only conv0 and conv9 carry a bias) and arithmetic follow
     codes/models/modules/architectures/discriminators.py:686-779: conv3(in->nf)+LReLU; three conv4s2 (no bias)+LReLU
     down to H/8; three times [bilinear x2 (align_corners=False) -> conv3 (no bias) + LReLU -> + skip]; two more
-    conv3 + LReLU; conv3(nf->1) with bias.  `spectral_norm` cannot be enabled from the options
-    (options/defaults.py:378-382 forwards only input_nc / nf / skip_connection) and is refused here.
+    conv3 + LReLU; conv3(nf->1) with bias.  `spectral_norm` wraps conv0 .. conv8 (conv9 stays plain) as the reference does
+    (discriminators.py:701-735): block.SpectralNormConv2dHIP, normalised once per forward by the engine (csrc/spectral_norm.hip).
 
     Kernels: the k3 / k4s2 implicit-GEMM tiles (conv_tile.hip) with the image-side layers on the vector ALUs;
     bilinear x2 and its adjoint as one HBM pass each (elementwise.hip).  The decoder activations are kept BEFORE the
@@ -163,13 +163,11 @@ class UNetDiscriminator(HipNet):
 
     def __init__(self, input_nc, nf=64, skip_connection=True, spectral_norm=False):
         super().__init__()
-        if spectral_norm:
-            raise NotImplementedError("spectral norm in UNetDiscriminator is not implemented by the HIP engine")
         if input_nc > 4 or nf % 4:
             raise NotImplementedError("HIP UNetDiscriminator needs <= 4 image channels and nf %% 4 == 0")
         self.input_nc, self.nf, self.skip_connection = input_nc, nf, bool(skip_connection)
         self.slope = 0.2
-        C = B.Conv2dHIP
+        C = B.SpectralNormConv2dHIP if spectral_norm else B.Conv2dHIP
         self.conv0 = C(input_nc, nf, 3, 1)
         self.conv1 = C(nf, nf * 2, 4, 2, bias=False)
         self.conv2 = C(nf * 2, nf * 4, 4, 2, bias=False)
@@ -179,7 +177,7 @@ class UNetDiscriminator(HipNet):
         self.conv6 = C(nf * 2, nf, 3, 1, bias=False)
         self.conv7 = C(nf, nf, 3, 1, bias=False)
         self.conv8 = C(nf, nf, 3, 1, bias=False)
-        self.conv9 = C(nf, 1, 3, 1)
+        self.conv9 = B.Conv2dHIP(nf, 1, 3, 1)
         self._init_engine()
 
     def _build_ops(self, packer):
@@ -237,7 +235,9 @@ class UNetDiscriminator(HipNet):
         x0, x1, x2, x3 = sv["enc"]
         ups, ys, xs, o7, o8 = sv["ups"], sv["ys"], sv["xs"], sv["o7"], sv["o8"]
         N, H, W = x4.N, x4.H, x4.W
-        sched = getattr(self, "_bucket_schedule", None) if Wg else None      # data-parallel gradient buckets (dp.py)
+        # data-parallel gradient buckets (dp.py); with spectral norm the parameter gradients are final only after the engine's
+        # correction launches behind this pass, and the exchange waits for the flush
+        sched = getattr(self, "_bucket_schedule", None) if (Wg and self._sn is None) else None
 
         def done(i):
             if sched is not None:
@@ -399,28 +399,32 @@ class NLayerDiscriminator(HipNet):
     """PatchGAN discriminator (Pix2Pix / CycleGAN) on the MI355X engine.
 
     Constructor, `state_dict` keys (`model.<i>.*`) and arithmetic follow codes/models/modules/architectures/
-    discriminators.py:472-579 for the default configuration get_network builds (BatchNorm2d, patch output, no spectral norm,
-    no intermediate feature maps): conv4 s2 (in -> ndf, bias) + LReLU; n_layers-1 x [conv4 s2 (no bias) + BN + LReLU];
-    conv4 s1 (no bias) + BN + LReLU; conv4 s1 (-> 1, bias).  The stride-2 layers run on the space-to-depth MFMA kernels
+    discriminators.py:472-579 for the configurations get_network builds (BatchNorm2d or spectral norm, patch output, no
+    intermediate feature maps): conv4 s2 (in -> ndf, bias) + LReLU; n_layers-1 x [conv4 s2 (no bias) + BN + LReLU];
+    conv4 s1 (no bias) + BN + LReLU; conv4 s1 (-> 1, bias).  With `use_spectral_norm` every convolution is wrapped
+    (block.SpectralNormConv2dHIP) and the norm layers are parameter-free place holders (the reference's B.Identity), so the
+    `model.<i>` indices stay and the network is conv + LeakyReLU with the activation in the conv epilogue.  The stride-2 layers run on the space-to-depth MFMA kernels
     (conv_tile.hip), the two stride-1 4x4 layers through the patch matrix + 1x1 GEMM / shifted 3x3 weight-gradient windows
     (_K4S1); only a first layer with a channel count that is not a multiple of 4 would use the generic kernel (csrc/gconv.hip)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=None, use_sigmoid=False, get_feats=False, patch=True,
                  use_spectral_norm=False):
         super().__init__()
-        if use_sigmoid or get_feats or not patch or use_spectral_norm or norm_layer is not None:
-            raise NotImplementedError("HIP NLayerDiscriminator implements the default PatchGAN (BatchNorm, patch output)")
+        if use_sigmoid or get_feats or not patch or norm_layer is not None:
+            raise NotImplementedError("HIP NLayerDiscriminator implements the default PatchGAN (BatchNorm or spectral norm, patch output)")
         if input_nc > 8 or ndf % 8:
             raise NotImplementedError("HIP NLayerDiscriminator needs <= 8 input channels and ndf %% 8 == 0")
         self.input_nc, self.n_layers, self.slope = input_nc, n_layers, 0.2
-        seq = [B.Conv2dHIP(input_nc, ndf, 4, 2), B.Marker("act:leakyrelu")]
+        C = B.SpectralNormConv2dHIP if use_spectral_norm else B.Conv2dHIP
+        norm = (lambda c: B.Marker("identity")) if use_spectral_norm else B.BatchNorm2dHIP
+        seq = [C(input_nc, ndf, 4, 2), B.Marker("act:leakyrelu")]
         nf_mult = 1
         for n in range(1, n_layers):
             prev, nf_mult = nf_mult, min(2 ** n, 8)
-            seq += [B.Conv2dHIP(ndf * prev, ndf * nf_mult, 4, 2, bias=False), B.BatchNorm2dHIP(ndf * nf_mult), B.Marker("act:leakyrelu")]
+            seq += [C(ndf * prev, ndf * nf_mult, 4, 2, bias=False), norm(ndf * nf_mult), B.Marker("act:leakyrelu")]
         prev, nf_mult = nf_mult, min(2 ** n_layers, 8)
-        seq += [B.Conv2dHIP(ndf * prev, ndf * nf_mult, 4, 1, bias=False), B.BatchNorm2dHIP(ndf * nf_mult), B.Marker("act:leakyrelu")]
-        seq += [B.Conv2dHIP(ndf * nf_mult, 1, 4, 1)]
+        seq += [C(ndf * prev, ndf * nf_mult, 4, 1, bias=False), norm(ndf * nf_mult), B.Marker("act:leakyrelu")]
+        seq += [C(ndf * nf_mult, 1, 4, 1)]
         self.model = nn.Sequential(*seq)
         self._init_engine()
 
@@ -431,7 +435,8 @@ class NLayerDiscriminator(HipNet):
         while i < len(mods):
             conv = mods[i]
             bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], B.BatchNorm2dHIP) else None
-            j = i + (2 if bn is not None else 1)
+            ident = bn is None and i + 1 < len(mods) and isinstance(mods[i + 1], B.Marker) and mods[i + 1].what == "identity"
+            j = i + (2 if (bn is not None or ident) else 1)
             act = j < len(mods) and isinstance(mods[j], B.Marker)
             if conv.in_channels % 4 == 0:
                 op = ConvOp(conv, packer, need_dgrad=True) if conv.stride == 2 else _K4S1(conv, packer, conv.in_channels)
@@ -506,7 +511,7 @@ class NLayerDiscriminator(HipNet):
         last = tape[-1][2]
         gy = View(new_act(N, last.H, last.W, last.C, dev))
         ops.nchw_to_nhwc(gout, gy, Cpad=last.C)
-        sched = getattr(self, "_bucket_schedule", None) if Wg else None
+        sched = getattr(self, "_bucket_schedule", None) if (Wg and self._sn is None) else None     # (see UNetDiscriminator)
         for li in range(len(self._layers) - 1, -1, -1):
             conv, bn, act, op = self._layers[li]
             xin, z, y, stats = tape[li]

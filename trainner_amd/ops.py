@@ -210,6 +210,87 @@ class DensePacker:
 
 
 # ----------------------------------------------------------------------------------------------
+# spectral normalisation (csrc/spectral_norm.hip)
+# ----------------------------------------------------------------------------------------------
+SN_ROWS_PER_TILE, SN_COLS_PER_TILE, SN_COLS_PER_SUM, SN_ROWS_PER_DOT, SN_CHUNK = 16, 1024, 256, 4, 4096
+SN_EPS = 1e-12
+_SN_FIELDS = ("w", "wn", "u", "v", "ru", "rv", "sig", "g", "dw")
+
+
+class SpectralNormTable:
+    """The device job table and tile tables of tnr_sn_forward / tnr_sn_backward for the wrapped layers of one network.
+    layers: one dict per layer with the fp32 tensors w [rows, ...] (the parameter), wn (derived, same shape), u [rows], v [K], the record
+    ru [rows], rv [K], sig [1], and for the backward g (gradient w.r.t. wn) and dw (the parameter's gradient); g / dw may be None for a
+    table that is only run forward."""
+
+    def __init__(self, layers, device):
+        self.layers, self.device = list(layers), device
+        self._ptrs = None
+
+    def dims(self, i):
+        w = self.layers[i]["w"]
+        return w.shape[0], w.numel() // w.shape[0]
+
+    def _build(self):
+        words = hip.load().tnr_sn_job_words()
+        assert words == 16
+        n_t = n_s = n_g = n_c = 0
+        geo = []
+        for i in range(len(self.layers)):
+            rows, K = self.dims(i)
+            nrb, nch = (rows + SN_ROWS_PER_TILE - 1) // SN_ROWS_PER_TILE, (rows * K + SN_CHUNK - 1) // SN_CHUNK
+            geo.append((rows, K, nrb, nch, n_t, n_g, n_s, n_c))
+            n_t, n_g, n_s, n_c = n_t + nrb * K, n_g + nch, n_s + rows, n_c + (K + SN_COLS_PER_SUM - 1) // SN_COLS_PER_SUM
+        self.ws64 = torch.zeros(n_t + n_g + n_c, dtype=torch.float64, device=self.device)
+        self.ws32 = torch.zeros(n_s, dtype=torch.float32, device=self.device)
+        jobs, wt, colt, rowt, chunks = [], [], [], [], []
+        for i, (L, (rows, K, nrb, nch, o_t, o_g, o_s, o_c)) in enumerate(zip(self.layers, geo)):
+            for f in _SN_FIELDS:
+                t = L.get(f)
+                assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == self.ws32.device), f
+            assert L["wn"].numel() == rows * K and L["u"].numel() == L["ru"].numel() == rows and L["v"].numel() == L["rv"].numel() == K
+            assert L.get("g") is None or L["g"].numel() == rows * K == L["dw"].numel()
+            jobs.append([hip.ptr(L.get(f)) or 0 for f in _SN_FIELDS] +
+                        [rows, K, self.ws64.data_ptr() + 8 * o_t, self.ws32.data_ptr() + 4 * o_s, self.ws64.data_ptr() + 8 * (n_t + o_g), nch,
+                         self.ws64.data_ptr() + 8 * (n_t + n_g + o_c)])
+            for b in range(nrb):
+                wt += [(i, b * SN_ROWS_PER_TILE, k0, b) for k0 in range(0, K, SN_COLS_PER_TILE)]
+            colt += [(i, k0, 0, c) for c, k0 in enumerate(range(0, K, SN_COLS_PER_SUM))]
+            rowt += [(i, r0, 0, 0) for r0 in range(0, rows, SN_ROWS_PER_DOT)]
+            chunks += [(i, c * SN_CHUNK, 0, c) for c in range(nch)]
+        self.njobs, self.n_wt, self.n_col, self.n_row, self.nchunks = len(jobs), len(wt), len(colt), len(rowt), len(chunks)
+        self.jobs = torch.tensor(jobs, dtype=torch.int64).reshape(-1, words).to(self.device)
+        self.wt = torch.tensor(wt, dtype=torch.int32).reshape(-1, 4).to(self.device)
+        self.colt = torch.tensor(colt, dtype=torch.int32).reshape(-1, 4).to(self.device)
+        self.rowt = torch.tensor(rowt, dtype=torch.int32).reshape(-1, 4).to(self.device)
+        self.chunks = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 4).to(self.device)
+        self._ptrs = self._live_ptrs()
+
+    def _live_ptrs(self):
+        return [hip.ptr(L.get(f)) for L in self.layers for f in _SN_FIELDS]
+
+    def ensure(self):
+        if self._ptrs is None or self._ptrs != self._live_ptrs():
+            self._build()
+        return self
+
+
+def sn_forward(table, iterate, eps=SN_EPS):
+    """Every layer of the table: (iterate: v <- normalize(W^T u), u <- normalize(W v) in place;) sigma = u . (W v); wn = W / sigma; the
+    record (ru, rv, sig) filled.  4 launches with iterate, else 2, whatever the layer count."""
+    t = table.ensure()
+    hip.check(hip.load().tnr_sn_forward(t.jobs.data_ptr(), t.njobs, t.wt.data_ptr(), t.n_wt, t.colt.data_ptr(), t.n_col, t.rowt.data_ptr(), t.n_row,
+                                        t.chunks.data_ptr(), t.nchunks, int(bool(iterate)), eps, hip.stream()), "sn_forward")
+
+
+def sn_backward(table):
+    """Every layer of the table: dw += (g - <g, wn> ru rv^T) / sig.  2 launches."""
+    t = table.ensure()
+    assert all(L.get("g") is not None and L.get("dw") is not None for L in t.layers)
+    hip.check(hip.load().tnr_sn_backward(t.jobs.data_ptr(), t.njobs, t.chunks.data_ptr(), t.nchunks, hip.stream()), "sn_backward")
+
+
+# ----------------------------------------------------------------------------------------------
 # convolution
 # ----------------------------------------------------------------------------------------------
 class ConvProfile:

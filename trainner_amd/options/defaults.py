@@ -119,6 +119,10 @@ def get_network_D_config(network_D, scale, crop_size, model_G):
         full["input_nc"] = src.pop("in_nc", 3)
         full["nf"] = src.pop("nf", 64)
         full["skip_connection"] = src.pop("skip_connection", True)
+        # engine extension: the reference's parser drops `spectral_norm` for this discriminator; here a key the user
+        # gave reaches the constructor, and an absent key leaves the parsed dictionary exactly as the reference's
+        if "spectral_norm" in src:
+            full["spectral_norm"] = bool(src.pop("spectral_norm"))
     else:
         raise NotImplementedError("Discriminator model [{}] is outside the SR hot path of the HIP engine".format(kind))
     if src:
