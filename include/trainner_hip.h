@@ -799,6 +799,11 @@ int tnr_ranger_step_guarded(float *p, const float *g, float *m, float *v, float 
                             const int64_t *segs, int32_t nseg, const int32_t *rowseg, int64_t nrows, void *ws, int64_t ws_bytes,
                             int32_t gc_min_dim, double b1, double b2, float eps, float weight_decay, float step, int32_t rectified,
                             int32_t lookahead, float alpha, const uint32_t *fault, void *stream);
+/* Stochastic weight averaging (torch.optim.swa_utils.AveragedModel; swa.py:4-23): avg <- lerp(avg, p, weight) in ATen's form,
+ * weight < 0.5 ? avg + weight (p - avg) : p - (p - avg)(1 - weight), with weight = fp32(1 / (n_averaged + 1)).  weight 1 copies p
+ * exactly; p == avg leaves avg's bits.  One launch over all n floats of a flat buffer (alignment gaps included), behind *fault as
+ * tnr_adam_step_guarded (fault may be NULL): the average never absorbs a step that was not applied.  p is only read. */
+int tnr_swa_update_guarded(float *avg, const float *p, int64_t n, float weight, const uint32_t *fault, void *stream);
 /* --- spectral normalisation of convolution weights (csrc/spectral_norm.hip; torch.nn.utils.spectral_norm, one power iteration, dim 0) ---
  * jobs [njobs][tnr_sn_job_words()] int64, one row per wrapped layer: w, wn, u, v, ru, rv, sig, g, dw (device addresses), rows, K,
  * tpart (double [ceil(rows / 16)][K]), s (float [rows]), gpart (double [ngpart]), ngpart, sspart (double [ceil(K / 256)]).  w is the [rows][K] parameter, wn the derived

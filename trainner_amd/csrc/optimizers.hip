@@ -414,6 +414,36 @@ __global__ void ranger_kernel(float *p, const float *g, float *m, float *v, floa
     }
 }
 
+// ---------------------------------------------------------------------------------- stochastic weight averaging
+// torch.optim.swa_utils.AveragedModel's running mean, avg.lerp_(p, w) with w = fp32(1 / (n_averaged + 1)), in ATen's lerp form:
+// w = 1 copies p exactly, p == avg leaves avg's bits alone.  A pure stream over the WHOLE flat buffer (alignment gaps included: they
+// are zero in both buffers and stay zero), 12 bytes per element: 256 threads x 16 bytes per block, at most MAX_GRID blocks, the rest
+// by grid-stride.  VEC needs both pointers 16-byte aligned (flat buffers are); the n % 4 tail elements go to the first block.
+__device__ __forceinline__ float swa_lerp(float a, float p, float w) {
+    const float d = p - a;
+    return w < 0.5f ? a + w * d : p - d * (1.f - w);
+}
+
+template <bool VEC>
+__global__ void swa_update_kernel(float *avg, const float *p, int64_t n, float w, const unsigned *fault) {
+    TNR_LATCH(fault);
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += stride) {
+            const f32x4 pv = reinterpret_cast<const f32x4 *>(p)[i];
+            f32x4 av = reinterpret_cast<f32x4 *>(avg)[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) av[k] = swa_lerp(av[k], pv[k], w);
+            reinterpret_cast<f32x4 *>(avg)[i] = av;
+        }
+        const int64_t e = (n4 << 2) + tid;
+        if (tid < 4 && e < n) avg[e] = swa_lerp(avg[e], p[e], w);
+    } else {
+        for (int64_t e = tid; e < n; e += stride) avg[e] = swa_lerp(avg[e], p[e], w);
+    }
+}
+
 inline unsigned grid_chunks(int64_t n) { return (unsigned)(n > MAX_GRID ? MAX_GRID : (n < 1 ? 1 : n)); }
 inline unsigned grid_rows(int64_t nrows) { return grid_chunks(tnr_cdiv64(nrows, 4)); }
 
@@ -509,4 +539,15 @@ extern "C" int tnr_ranger_step_guarded(float *p, const float *g, float *m, float
                        (const Seg *)segs, (const float *)rowmean, gc_min_dim, (float)b1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), eps,
                        weight_decay, step, rectified, lookahead, alpha, (const unsigned *)fault);
     return tnr_check_launch("ranger");
+}
+
+extern "C" int tnr_swa_update_guarded(float *avg, const float *p, int64_t n, float weight, const uint32_t *fault, void *stream) {
+    TNR_REQUIRE(avg && p && n > 0, "swa_update: bad arguments");
+    TNR_REQUIRE(weight > 0.f && weight <= 1.f, "swa_update: weight %g is not 1 / (n_averaged + 1)", (double)weight);
+    const unsigned grid = grid_chunks(tnr_cdiv64(n, 1024));
+    if ((((uintptr_t)avg | (uintptr_t)p) & 15) == 0)
+        hipLaunchKernelGGL(swa_update_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, avg, p, n, weight, (const unsigned *)fault);
+    else
+        hipLaunchKernelGGL(swa_update_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, avg, p, n, weight, (const unsigned *)fault);
+    return tnr_check_launch("swa_update");
 }

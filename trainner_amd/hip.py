@@ -233,6 +233,7 @@ _SIGS = {
                                     c_f, c_f, c_f, c_p, c_p]),
     "tnr_ranger_step_guarded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_l, c_p, c_l, c_i, C.c_double, C.c_double,
                                       c_f, c_f, c_f, c_i, c_i, c_f, c_p, c_p]),
+    "tnr_swa_update_guarded": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p]),
     "tnr_sn_job_words": (c_i, []),
     "tnr_sn_forward": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_f, c_p]),
     "tnr_sn_backward": (c_i, [c_p, c_i, c_p, c_i, c_p]),

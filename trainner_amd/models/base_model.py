@@ -5,8 +5,8 @@ state_dicts with `latest_/previous_` rotation (:353-443), training-state save/re
 scheduler plumbing (:209-317), `requires_grad` (:325-351), the `setup_*` feature switches (:641-787) and
 `calc_gradients` / `optimizer_step` / `backward_D_Basic` / `apply_gradclip` (:805-922).
 Re-designed: gradient clipping and Adam act on the flat buffers (2 + 1 launches per network), the
-data-parallel gradient exchange happens inside `optimizer_step`, AMP/SWA/CEM/ATG/batch-aug switches
-raise if enabled (they are off in the ESRGAN recipe and outside the hot path, SURVEY.md 2 #18,#24).
+data-parallel gradient exchange happens inside `optimizer_step`, stochastic weight averaging keeps one flat
+buffer and makes one launch per step (models/swa.py), the CEM/ATG switches raise if enabled.
 """
 import logging
 import os
@@ -146,6 +146,17 @@ class BaseModel:
             return
         for name in self.model_names:
             self.save_network(getattr(self, "net" + name), name, iter_step, latest)
+        if self.swa:
+            # base_model.py:174-189 moves the averaged model to the CPU for update_bn(loader, ...) and back; update_bn returns at once
+            # for a generator without BatchNorm and one with BatchNorm is refused at set-up (setup_swa): `loader` is not read
+            self.save_network(self.swa_model, "swaG", iter_step, latest)
+
+    def load_swa(self):
+        """base_model.py:209-214: `pretrain_model_swaG` (check_resume sets it next to a .state file), loaded strictly."""
+        load_path = self.opt["path"].get("pretrain_model_swaG") if self.opt["is_train"] and self.opt.get("use_swa") else None
+        if load_path is not None:
+            logger.info("Loading pretrained model for SWA G [%s]", load_path)
+            self.load_network(load_path, self.swa_model)
 
     def load(self):
         for name in self.model_names:
@@ -189,6 +200,8 @@ class BaseModel:
             return
         state = {"epoch": epoch, "iter": iter_step, "schedulers": [s.state_dict() for s in self.schedulers],
                  "optimizers": [o.state_dict() for o in self.optimizers]}
+        if self.opt["is_train"] and self.opt.get("use_swa"):      # base_model.py:461-465: empty until the SWA regime has begun
+            state["swa_scheduler"] = [self.swa_scheduler.state_dict()] if self._swa_regime(iter_step) else []
         # engine-only entry (the reference's resume reads the four keys above and ignores the rest): the position of every network's
         # counter-based ESRGAN+ noise stream, so that a resumed run continues the stream instead of replaying it from forward 0
         noise = {name: [getattr(getattr(self, "net" + name), "_noise_calls"), getattr(getattr(self, "net" + name), "noise_seed")]
@@ -212,6 +225,9 @@ class BaseModel:
             if hasattr(s, "milestones") and isinstance(s.milestones, Counter) and isinstance(st.get("milestones"), list):
                 st["milestones"] = Counter(st["milestones"])
             s.load_state_dict(st)
+        if self.opt["is_train"] and self.opt.get("use_swa"):
+            for st in resume_state.get("swa_scheduler", None) or []:
+                self.swa_scheduler.load_state_dict(st)
         for name, (calls, seed) in (resume_state.get("tnr_engine") or {}).get("noise_streams", {}).items():
             net = getattr(self, "net" + name, None)
             if net is not None and hasattr(net, "_noise_calls"):
@@ -238,16 +254,30 @@ class BaseModel:
     def _get_init_lr(self):
         return [[g["initial_lr"] for g in o.param_groups] for o in self.optimizers]
 
+    def _swa_regime(self, current_step):
+        """base_model.py:254-256: SWA is on and `current_step` is past `swa_start_iter`."""
+        return bool(self.swa and current_step and isinstance(self.swa_start_iter, int) and current_step > self.swa_start_iter)
+
     def update_learning_rate(self, current_step=None, warmup_iter=-1):
-        for s in self.schedulers:
-            s.step()
-        if current_step is not None and current_step < warmup_iter:
-            self._set_lr([[v / warmup_iter * current_step for v in grp] for grp in self._get_init_lr()])
+        if self._swa_regime(current_step):
+            # base_model.py:254-273: the step's weights enter the average, the SWA scheduler steps in place of G's own (the first
+            # scheduler), the others go on as before; no warm-up in this regime
+            self.swa_model.update_parameters(self.netG)
+            self.swa_scheduler.step()
+            for s in self.schedulers[1:]:
+                s.step()
+        else:
+            for s in self.schedulers:
+                s.step()
+            if current_step is not None and current_step < warmup_iter:
+                self._set_lr([[v / warmup_iter * current_step for v in grp] for grp in self._get_init_lr()])
         self.optGstep = False
         if self.cri_gan:
             self.optDstep = False
 
     def get_current_learning_rate(self, current_step=None):
+        if self._swa_regime(current_step):
+            return self.swa_scheduler.get_last_lr()[0]
         return self.schedulers[0].get_last_lr()[0]
 
     def requires_grad(self, model, flag=True, target_layer=None, net_type=None):
@@ -340,8 +370,48 @@ class BaseModel:
         self.schedulers = schedulers.get_schedulers(optimizers=self.optimizers, train_opt=self.opt["train"])
 
     def setup_swa(self):
-        self.swa = None
-        self._reject(self.opt.get("use_swa"), "SWA (use_swa)")
+        """base_model.py:702-720: `use_swa` builds the averaged generator and the SWA scheduler at construction (trainner_amd/models/
+        swa.py) and loads `pretrain_model_swaG`.  The average is one flat buffer updated by one launch per step."""
+        train_opt = self.opt["train"]
+        self.swa = self.opt.get("use_swa")
+        if not self.swa:
+            return
+        from . import swa
+        bn = [n for n, m in self.netG.named_modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+        if bn:
+            raise NotImplementedError(
+                "SWA (use_swa) with a generator that contains BatchNorm layers ({} has {}, first: {}) is not implemented by the HIP "
+                "engine: the reference's save() hands the loader's dict batches to the network in torch.optim.swa_utils.update_bn and "
+                "fails there".format(type(self.netG).__name__, len(bn), bn[0]))
+
+        def opt_or(key, default):          # (a missing key of the parsed option tree reads as None)
+            return default if train_opt.get(key) is None else train_opt[key]
+
+        self.swa_start_iter = opt_or("swa_start_iter", 0)
+        swa_lr = opt_or("swa_lr", 0.0001)
+        self.swa_scheduler, self.swa_model = swa.get_swa(self.optimizer_G, self.netG, swa_lr, opt_or("swa_anneal_epochs", 10),
+                                                         opt_or("swa_anneal_strategy", "cos"))
+        self.load_swa()
+        logger.info("SWA enabled. Starting on iter: %s, lr: %s", self.swa_start_iter, swa_lr)
+
+    @contextmanager
+    def swa_generator(self):
+        """Inside, netG holds the averaged weights (test() / test_x8() / test_chop() on the average without a file round trip); on exit
+        it holds the training weights again, bit for bit.  A copy out and a copy in of the flat buffer on entry, a copy back on exit, and
+        `holder.touch()` each way; not for use inside a step."""
+        if not self.swa:
+            raise RuntimeError("swa_generator() needs use_swa")
+        holder = self.swa_model._holder(self.netG)
+        keep = holder.flat.clone()
+        with torch.no_grad():
+            holder.flat.copy_(self.swa_model.flat)
+        holder.touch()
+        try:
+            yield self.netG
+        finally:
+            with torch.no_grad():
+                holder.flat.copy_(keep)
+            holder.touch()
 
     def setup_virtual_batch(self):
         ds = self.opt["datasets"]["train"]
@@ -421,6 +491,8 @@ class BaseModel:
         for o in self.optimizers:
             for mv in getattr(o, "_moments", {}).values():       # EVERY flat state buffer of the optimiser (optimizers.FusedFlatOptimizer)
                 tensors += list(mv)
+        if self.swa:                                             # every rank keeps an identical average
+            tensors += [self.swa_model.flat, self.swa_model.n_averaged.view(1)] + list(self.swa_model.buffers.values())
         # ESRGAN+ noise: ONE stream for all replicas (each rank draws the field of its own samples of the global batch): rank 0's
         # seed -- torch.initial_seed() differs per rank when manual_seed is unset -- and rank 0's position in the stream
         noisy = [getattr(self, "net" + n) for n in self.model_names if hasattr(getattr(self, "net" + n), "_noise_calls")]
@@ -436,6 +508,8 @@ class BaseModel:
                 net.noise_seed, net._noise_calls = int(vals[2 * i]), int(vals[2 * i + 1])
         for name in self.model_names:
             getattr(self, "net" + name).flat_params().touch()
+        if self.swa:
+            self.swa_model.resync()
 
     def _zero_frozen_grads(self, opt_flag):
         """Parameters with requires_grad False at step time (FreezeD: base_model.py:641-655, sr_model.py:249-253) get

@@ -1867,3 +1867,11 @@ def ranger_step(p, g, m, v, slow, table, lr, b1, b2, eps, wd, t, k=6, alpha=0.5,
     hip.check(hip.load().tnr_ranger_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), slow.data_ptr(), *_tbl_rows(table),
                                                  gc_min_dim, b1, b2, eps, wd, step_size * lr, int(rect), int(t % k == 0), alpha,
                                                  fault_word(p.device).data_ptr(), hip.stream()), "ranger_step")
+
+
+def swa_update(avg, p, n_averaged):
+    """Stochastic weight averaging over a flat buffer: avg <- lerp(avg, p, fp32(1 / (n_averaged + 1))), n_averaged the host count of
+    the updates made so far (0: avg becomes a copy of p).  One launch behind the fault latch."""
+    assert avg.numel() == p.numel() and avg.dtype == p.dtype == torch.float32 and avg.is_contiguous() and p.is_contiguous()
+    hip.check(hip.load().tnr_swa_update_guarded(avg.data_ptr(), p.data_ptr(), p.numel(), 1.0 / (int(n_averaged) + 1),
+                                                fault_word(p.device).data_ptr(), hip.stream()), "swa_update")

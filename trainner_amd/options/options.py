@@ -209,7 +209,8 @@ def check_resume(opt, resume_iter=None):
             if opt["path"].get("pretrain_model" + ptype + sufx):
                 logger.warning("pretrain_model%s%s path ignored, resuming training from a .state file.", ptype, sufx)
     idx = resume_iter if resume_iter else os.path.basename(opt["path"]["resume_state"]).split(".")[0]
-    targets = ["_G"] + (["_D"] if opt["train"]["gan_weight"] else [])
+    # `use_swa`: the averaged generator's file beside the generator's (options.py:702-703)
+    targets = ["_G"] + (["_swaG"] if opt.get("use_swa") else []) + (["_D"] if opt["train"]["gan_weight"] else [])
     for ptype in targets:
         for mkey in keys:
             path = os.path.normpath(os.path.join(opt["path"]["models"], "{}{}{}.pth".format(idx, ptype, mkey)))
