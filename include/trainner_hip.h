@@ -204,8 +204,8 @@ const char *tnr_last_error(void);
 /* ABI version = TNR_ABI_VERSION of the header the library was built from.  It moves whenever a descriptor struct changes size or
  * layout: a caller built against another header would pass a shorter struct and the library would read fields from adjacent memory.
  * Consumers compare it with THEIR header's TNR_ABI_VERSION before the first call (trainner_amd/hip.py does).
- *   1: rounds 1-4.   2: tnr_wgrad_desc gained dw2 / cout_split / cin_total2 / db2, TNR_WGRAD_GROUP_MAX 8 -> 12 (round 5; the number
- *      itself was bumped in round 6).   3: tnr_conv_desc gained wq_form and shuffle (round 6).                                      */
+ *   1: rounds 1-4.   2: tnr_wgrad_desc gained dw2 / cout_split / cin_total2 / db2, TNR_WGRAD_GROUP_MAX 8 -> 12 (round 5; the number itself
+ *      was bumped in round 6).   3: tnr_conv_desc gained wq_form and shuffle (round 6); tnr_wgrad_tile_class has since lost an argument: still 3. */
 #define TNR_ABI_VERSION 3
 int tnr_version(void);
 
@@ -335,10 +335,9 @@ int tnr_conv_wgrad(const tnr_wgrad_desc *d, void *stream);
 #define TNR_WGRAD_GROUP_MAX 12
 int tnr_conv_wgrad_group(const tnr_wgrad_desc *descs, int32_t n, void *stream);
 /* Host-only query, no device and no launch: the workgroup tile class tnr_conv_wgrad_group runs `d` on when its launch carries group_jobs
- * (cin block, cout block) jobs (0: the layer alone).  x3_occ: the value of TNR_WG_X3_OCC to plan for, < 0: the process's setting.
- * out = {mode, A_T, B_T, THG, BF, WPS, DB (the kernel's template arguments), KS, splits, tiles_per_split, LDS bytes, index of the class in
- * the library's table}.  Only d's shape fields, mode, mma, pad_mode and the views' ctot are read.  TNR_EINVAL: no kernel for this descriptor. */
-int tnr_wgrad_tile_class(const tnr_wgrad_desc *d, int32_t group_jobs, int32_t x3_occ, int32_t out[12]);
+ * (cin block, cout block) jobs (0: the layer alone).  out = {mode, A_T, B_T, THG, BF, WPS, DB (the kernel's template arguments), KS, splits,
+ * tiles_per_split, LDS bytes, index in the library's class table}.  Reads d's shape fields, mode, mma, pad_mode, the views' ctot.  TNR_EINVAL: no kernel. */
+int tnr_wgrad_tile_class(const tnr_wgrad_desc *d, int32_t group_jobs, int32_t out[12]);
 
 /* --- image-to-image family (Pix2Pix / CycleGAN: ResnetGenerator ResNet_arch.py:11-90, NLayerDiscriminator
  * discriminators.py:472-579).  Generic convolution on the vector ALUs for the layers outside the matrix-core geometries

@@ -2,7 +2,6 @@
 the class table existed (tests/golden/wgrad_classes.json, tools/record_wgrad_classes.py), through the host-only tnr_wgrad_tile_class.  No GPU."""
 import ctypes as C
 import json
-import os
 
 import pytest
 
@@ -18,24 +17,17 @@ def golden():
 
 @pytest.fixture(scope="module")
 def replay():
-    """The recorder's walk over this tree's library; the workspace bytes are derived from the query's split count (tnr_wgrad_workspace_bytes
-    itself only answers for the process's TNR_WG_X3_OCC: test_workspace_bytes)."""
+    """The recorder's walk over this tree's library."""
     lib = hip.load()
-
-    def ws_bytes(d, occ):
-        q = rec.query(lib, d, 0, occ)
-        s2d = d.mode == hip.CONV_4x4_S2
-        koutp, kinvp = -(-d.Cout // 32) * 32, -(-d.Cin // 32) * 32 * (4 if s2d else 1)
-        return 4 * q[8] * ((4 if s2d else 9) * koutp * kinvp + koutp)
-    return rec.walk(lib, ws_bytes)
+    return rec.walk(lib, lambda d: lib.tnr_wgrad_workspace_bytes(C.byref(d)))
 
 
 def test_grid_is_the_cross_product(golden):
     dims = golden["dims"]
-    assert dims == dict(mode=[0, 1, 2], cout=[32, 64], cin_blocks=[1, 2, 3, 4, 5, 6], mma=[0, 1, 2], x3_occ=[1, 2, 3], pad_mode=[0, 1],
+    assert dims == dict(mode=[0, 1, 2], cout=[32, 64], cin_blocks=[1, 2, 3, 4, 5, 6], mma=[0, 1, 2], pad_mode=[0, 1],
                         over=["none", "x", "g"])
-    assert [list(v) for v in (rec.MODES, rec.COUTS, rec.CIN_BLOCKS, rec.MMAS, rec.X3_OCCS, rec.PAD_MODES, rec.OVER)] == list(dims.values())
-    assert len(rec.GRID) == len(set(rec.GRID)) == 3 * 2 * 6 * 3 * 3 * 2 * 3 == len(golden["cells"])
+    assert [list(v) for v in (rec.MODES, rec.COUTS, rec.CIN_BLOCKS, rec.MMAS, rec.PAD_MODES, rec.OVER)] == list(dims.values())
+    assert len(rec.GRID) == len(set(rec.GRID)) == 3 * 2 * 6 * 3 * 2 * 3 == len(golden["cells"])
     assert golden["sizes"] == [list(s) for s in rec.SIZES] and golden["group_jobs"] == list(rec.GROUP_JOBS)
     assert all(len(row) == len(rec.SIZES) for row in golden["cells"])
     # the 2^30 dimension is real: "x" / "g" cells stand at or above the bound, and some "none" cell of every size below it
@@ -44,8 +36,8 @@ def test_grid_is_the_cross_product(golden):
             d = rec.desc(cell, size)
             nx, ng = d.N * d.H * d.W * d.x.ctot, d.N * d.Ho * d.Wo * d.g.ctot
             assert nx < 2 ** 31 and ng < 2 ** 31
-            if cell[6] != "none":
-                assert (nx if cell[6] == "x" else ng) >= 2 ** 30
+            if cell[5] != "none":
+                assert (nx if cell[5] == "x" else ng) >= 2 ** 30
             elif cell[0] == 0:
                 assert nx < 2 ** 30 and ng < 2 ** 30
 
@@ -69,38 +61,34 @@ def test_table_rows_are_the_recorded_classes(golden):
     rows = {}
     for cell in rec.GRID:
         for size in rec.SIZES[:1] + rec.SIZES[-1:]:
-            q = rec.query(lib, rec.desc(cell, size), 0, cell[4])
+            q = rec.query(lib, rec.desc(cell, size), 0)
             if q is not None:
                 assert rows.setdefault(q[11], tuple(q[:7])) == tuple(q[:7])
     assert set(rows.values()) == recorded
     assert sorted(rows) == list(range(len(recorded))), "a table row no descriptor reaches"          # indices 0 .. n-1, each seen
     out = (C.c_int32 * 12)()
-    d = rec.desc((0, 32, 4, 5, 1, 0, "none"), (1, 8, 8))          # an arithmetic the table has no row for: no kernel
-    assert lib.tnr_wgrad_tile_class(C.byref(d), 0, 1, C.byref(out)) == -1
+    d = rec.desc((0, 32, 4, 5, 0, "none"), (1, 8, 8))          # an arithmetic the table has no row for: no kernel
+    assert lib.tnr_wgrad_tile_class(C.byref(d), 0, C.byref(out)) == -1
     msg = lib.tnr_last_error().decode()
     assert "128 -> 32 channels" in msg and "mode 0" in msg
 
 
 def test_workspace_bytes(golden):
-    """tnr_wgrad_workspace_bytes answers for the process's TNR_WG_X3_OCC: every cell of that value."""
+    """tnr_wgrad_workspace_bytes itself, on every cell."""
     lib = hip.load()
-    occ = int(os.environ.get("TNR_WG_X3_OCC", "3"))
-    occ = 3 if occ >= 3 else 2 if occ == 2 else 1          # (the library compares >= 2 and == 3)
     n = 0
     for cell, row in zip(rec.GRID, golden["cells"]):
-        if cell[4] != occ:
-            continue
         for size, ri in zip(rec.SIZES, row):
             d = rec.desc(cell, size)
             assert lib.tnr_wgrad_workspace_bytes(C.byref(d)) == golden["records"][ri][1], (cell, size)
             n += 1
-    assert n == len(rec.GRID) // 3 * len(rec.SIZES)
+    assert n == len(rec.GRID) * len(rec.SIZES)
 
 
 def test_group_needs_one_class():
     """A 32-cout and a 64-cout layer do not share a launch: tnr_conv_wgrad_group compares the rows of the table."""
     lib = hip.load()
-    a, b = rec.desc((0, 32, 2, 0, 3, 0, "none"), (1, 16, 24)), rec.desc((0, 64, 2, 0, 3, 0, "none"), (1, 16, 24))
+    a, b = rec.desc((0, 32, 2, 0, 0, "none"), (1, 16, 24)), rec.desc((0, 64, 2, 0, 0, "none"), (1, 16, 24))
     qa, qb = ops.wgrad_tile_class(a), ops.wgrad_tile_class(b)
     assert qa["row"] != qb["row"] and (qa["a_t"], qb["a_t"]) == (1, 2)
     # through the launcher: host-side dummies pass the pointer check, the class comparison fails before anything touches a device

@@ -1464,7 +1464,6 @@ def test_bf16x3_split_operand_mode(monkeypatch):
         return to_nchw(ys, 0, 96)
     both("im2col splitk", small, F.conv2d(xs.to(d), ws_.to(d), None, padding=1))
     # weight gradients: every workgroup tile class (32 x 32/64/96/128 pixel-split and shared-pixel, 64 x 64, strided)
-    monkeypatch.setattr(ops, "WGRAD_X3", True)
     for (mode, Nn, Hh, Ww, ci, co) in (("3x3", 2, 32, 32, 32, 32), ("3x3", 1, 32, 48, 64, 32), ("3x3", 2, 16, 16, 96, 32),
                                        ("3x3", 1, 24, 32, 128, 32), ("3x3", 2, 16, 32, 192, 64), ("s2", 2, 16, 32, 64, 64)):
         xx = rnd(Nn, ci, Hh, Ww, seed=11)

@@ -1,4 +1,4 @@
-"""One launch on every weight-gradient tile class (csrc/wgrad_tile.hip WG_ROWS) a small tensor reaches at the default TNR_WG_X3_OCC, in the
+"""One launch on every weight-gradient tile class (csrc/wgrad_tile.hip WG_ROWS), in the
 arithmetic of the row, against torch.autograd.grad on the CPU under test_wgrad's criterion: 5e-5 x (max |ref| + 1) for dw and db, alpha = 0.5,
 beta = 1 over a random start.  TNR_MMA_BF16 rounds its operands to bf16 in front of the matrix core and their products are exact in fp32, so its
 rows are held to the same criterion against autograd on the bf16-ROUNDED x and g (db: the fp32 sum of the un-rounded gradient), as
@@ -7,10 +7,12 @@ test_bf16_operand_mode does.  Before the launch the case asserts, through tnr_wg
 Shapes, the smallest at which a class can still go wrong: N = 1, 20 x 18 outputs (two tile columns with a ragged edge, more than one tile row for
 every THG <= 16); the 4x4-s2 mode from a 24 x 36 input, nearest-x2 from 10 x 9.
 
-Rows only tests/test_cpu_wgrad_plan.py covers: the ten TNR_MMA_BF16X3 rows of the 3x3 modes with WPS = 1 and DB = 0 and the 4x4-s2 row
-{2, 2, 8, BF 2} (all TNR_WG_X3_OCC=1: the switch is read once per process).  The half-height two-workgroup rows of TNR_CONV_3x3, which zero-padded
-launches reach only from 2^30 elements on, run here through reflection padding.
+The half-height two-workgroup rows of TNR_CONV_3x3, which zero-padded launches reach only from 2^30 elements on, run here through reflection
+padding.  test_cases_cover_the_table: no row of the table is left to tests/test_cpu_wgrad_plan.py alone.
 """
+import json
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -85,6 +87,23 @@ def test_row(case, monkeypatch):
     print("dw err %.3e (bound %.3e)  db err %.3e (bound %.3e)" % (err_w, 5e-5 * (ref_w.abs().max().item() + 1), err_b, 5e-5 * (ref_b.abs().max().item() + 1)))
     assert err_w <= 5e-5 * (ref_w.abs().max().item() + 1.0), "wgrad weights"
     assert err_b <= 5e-5 * (ref_b.abs().max().item() + 1.0), "wgrad bias"
+
+
+def test_cases_cover_the_table(monkeypatch):
+    """CASES lands on every row of WG_ROWS: the rows its descriptors name through the host-only query (no launch, shapes only) are 0 .. n - 1,
+    n the number of classes of the recorded table (tests/golden/wgrad_classes.json), whose classes tests/test_cpu_wgrad_plan.py holds equal
+    to the table's rows."""
+    from trainner_amd import ops
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_classes.json")) as f:
+        n = len([c for c in json.load(f)["classes"] if c is not None])
+    rows = set()
+    for mode, mma, cin, cout, reflect, row in CASES:
+        monkeypatch.setattr(ops, "MMA", mma)
+        k = 4 if mode == "s2" else 3
+        (H, W), (Ho, Wo) = {"3x3": ((20, 18), (20, 18)), "up2": ((10, 9), (20, 18)), "s2": ((24, 36), (12, 18))}[mode]
+        item = dict(x=ops.View(torch.empty(1, H, W, cin)), g=ops.View(torch.empty(1, Ho, Wo, cout)), dw=torch.empty(cout, cin, k, k), reflect=reflect)
+        rows.add(lands_on(ops, item, mode, mma, row)["row"])
+    assert rows == set(range(n))
 
 
 @pytest.mark.parametrize("mma", [F32, BF16, X3])

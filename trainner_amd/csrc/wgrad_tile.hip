@@ -614,7 +614,8 @@ wgrad_tile_kernel(const WgK ga) {
                 if constexpr (BF == 2) {
                     // TNR_MMA_BF16X3: both tiles are pre-split in LDS (wg_x3_off); a fragment = 6 transposing reads (2 x 4 pixels x 3
                     // planes), six MFMAs per output tile and tile row.  The J tiles of a wave are taken two at a time (two independent
-                    // accumulator chains); the fragments of the next pair are read while the current pair's 12 MFMAs run.
+                    // accumulator chains).
+                    static_assert(WPS == 2, "TNR_MMA_BF16X3 outside the pipelined form (DB) runs two workgroups per CU");
                     constexpr int NP = (J + 1) / 2;
                     constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
                     // lane roles of the transposing read: 16-lane group -> (pixel half h = lane >> 5, channel half cg); inside the group
@@ -649,20 +650,18 @@ wgrad_tile_kernel(const WgK ga) {
                         const int P = xpix[j] + lpix;
                         return s_xb + (P >> 2) * ((CIB / 32) * 768) + (P & 3) * 64 + xblk[j] + lblk;
                     };
-                    // (two workgroups per CU: the other workgroup's wave covers the LDS latency, one fragment set is enough -- 24 registers)
-                    constexpr int NSET = WPS == 1 ? 2 : 1;
-                    wg_bf16x8 ca[3], cb[NSET][2][3];
-                    auto read_pair = [&](int jp, int set) {
+                    // (the other workgroup's wave covers the LDS latency: one fragment set, 24 registers, read in front of its pair)
+                    wg_bf16x8 ca[3], cb[2][3];
+                    auto read_pair = [&](int jp) {
     #pragma unroll
                         for (int q = 0; q < 2; ++q) {
                             const int j = 2 * jp + q < J ? 2 * jp + q : J - 1;
-                            frag(xaddr(j), cb[set][q], XB_RD);
+                            frag(xaddr(j), cb[q], XB_RD);
                         }
                     };
     #pragma unroll 1
                     for (int r = 0; r < ROWS; ++r) {
                         frag(ga_ptr, ca, GA_RD);
-                        if (NSET == 2) read_pair(0, 0);
                         if (want_bias) {           // hi + mid + lo reconstructs the fp32 value exactly
                             float brow = 0.f;      // (a tile row's 8 values first: see the fp32 k-loop)
     #pragma unroll
@@ -671,15 +670,13 @@ wgrad_tile_kernel(const WgK ga) {
                         }
     #pragma unroll
                         for (int jp = 0; jp < NP; ++jp) {
-                            if (NSET == 1) read_pair(jp, 0);
-                            else if (jp + 1 < NP) read_pair(jp + 1, (jp + 1) & 1);
+                            read_pair(jp);
                             __builtin_amdgcn_sched_barrier(0);
-                            const int cs = NSET == 1 ? 0 : (jp & 1);
     #pragma unroll
                             for (int p = 0; p < 6; ++p) {
-                                acc[2 * jp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ca[TA[p]], cb[cs][0][TB[p]], acc[2 * jp], 0, 0, 0);
+                                acc[2 * jp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ca[TA[p]], cb[0][TB[p]], acc[2 * jp], 0, 0, 0);
                                 if (2 * jp + 1 < J)
-                                    acc[2 * jp + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ca[TA[p]], cb[cs][1][TB[p]], acc[2 * jp + 1], 0, 0, 0);
+                                    acc[2 * jp + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ca[TA[p]], cb[1][TB[p]], acc[2 * jp + 1], 0, 0, 0);
                             }
                             __builtin_amdgcn_sched_barrier(0);
                         }
@@ -922,7 +919,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const RedK ga) {
     }
 }
 
-// ---- Tile classes.  One row per instantiation of wgrad_tile_kernel: exactly the classes some descriptor reaches under some TNR_WG_X3_OCC
+// ---- Tile classes.  One row per instantiation of wgrad_tile_kernel: exactly the classes some descriptor reaches
 // (tests/test_cpu_wgrad_plan.py).  plan_wgrad names a row, the LDS size and the slab geometry are computed from the row, and the launch walks
 // the table, so a kernel is instantiated only for a row and a plan can only run the kernel it sized its slabs for.
 struct WgRow { int mode, a_t, b_t, thg, bf, wps; bool db; };
@@ -936,18 +933,16 @@ constexpr WgRow WG_ROWS[] = {
     {M3, 1, 1, 16, 1, 1}, {M3, 1, 2, 16, 1, 1}, {M3, 1, 3, 4, 1, 2}, {M3, 1, 4, 8, 1, 1}, {M3, 2, 1, 16, 1, 1}, {M3, 2, 2, 8, 1, 1},
     {MU, 1, 1, 16, 0, 1}, {MU, 1, 2, 16, 0, 1}, {MU, 1, 3, 4, 0, 2}, {MU, 1, 4, 8, 0, 1}, {MU, 2, 1, 16, 0, 1}, {MU, 2, 2, 8, 0, 1},
     {MU, 1, 1, 16, 1, 1}, {MU, 1, 2, 16, 1, 1}, {MU, 1, 3, 4, 1, 2}, {MU, 1, 4, 8, 1, 1}, {MU, 2, 1, 16, 1, 1}, {MU, 2, 2, 8, 1, 1},
-    // TNR_MMA_BF16X3, the 3x3 modes.  32x96 at every TNR_WG_X3_OCC; then TNR_WG_X3_OCC=1: the fp32 classes, 32x64 at half height (the
-    // pre-split image takes 6 bytes per element: 16 rows would not fit the 160 KB)
-    {M3, 1, 3, 4, 2, 2}, {M3, 1, 1, 16, 2, 1}, {M3, 1, 2, 8, 2, 1}, {M3, 1, 4, 8, 2, 1}, {M3, 2, 1, 16, 2, 1}, {M3, 2, 2, 8, 2, 1},
-    {MU, 1, 3, 4, 2, 2}, {MU, 1, 1, 16, 2, 1}, {MU, 1, 2, 8, 2, 1}, {MU, 1, 4, 8, 2, 1}, {MU, 2, 1, 16, 2, 1}, {MU, 2, 2, 8, 2, 1},
-    // TNR_WG_X3_OCC >= 2: half-height tiles, two workgroups per CU
+    // TNR_MMA_BF16X3, the 3x3 modes: 32x96 as above (the pre-split image takes 6 bytes per element: 74 KB)
+    {M3, 1, 3, 4, 2, 2}, {MU, 1, 3, 4, 2, 2},
+    // every other width at half height (8 rows for 32x32, 4 otherwise; 32x128 runs as 32x64 jobs), two workgroups per CU
     {M3, 1, 1, 8, 2, 2}, {M3, 1, 2, 4, 2, 2}, {M3, 2, 1, 4, 2, 2}, {M3, 2, 2, 4, 2, 2},
     {MU, 1, 1, 8, 2, 2}, {MU, 1, 2, 4, 2, 2}, {MU, 2, 1, 4, 2, 2}, {MU, 2, 2, 4, 2, 2},
-    // TNR_WG_X3_OCC=3 (default), zero-padded 3x3 below 2^30 elements: the pipelined one-workgroup form with two tile sets
+    // the same tiles, zero-padded 3x3 below 2^30 elements: the pipelined one-workgroup form with two tile sets
     {M3, 1, 1, 8, 2, 1, true}, {M3, 1, 2, 4, 2, 1, true}, {M3, 2, 1, 4, 2, 1, true}, {M3, 2, 2, 4, 2, 1, true},
-    // 4x4 s2 (four virtual 32-channel blocks per 32 input channels): 32x128 and 64x64, two workgroups per CU; the last row is TNR_MMA_BF16X3
-    // with TNR_WG_X3_OCC >= 2 (the 8-row pre-split image is 109 KB: one workgroup per CU and nothing hides the refill; 4 rows: 58 KB, two)
-    {MS, 1, 4, 4, 0, 2}, {MS, 2, 2, 8, 0, 2}, {MS, 1, 4, 4, 1, 2}, {MS, 2, 2, 8, 1, 2}, {MS, 1, 4, 4, 2, 2}, {MS, 2, 2, 8, 2, 2}, {MS, 2, 2, 4, 2, 2},
+    // 4x4 s2 (four virtual 32-channel blocks per 32 input channels): 32x128 and 64x64, two workgroups per CU; TNR_MMA_BF16X3 takes 64x64 at
+    // 4 rows (the 8-row pre-split image is 109 KB: one workgroup per CU and nothing hides the refill; 4 rows: 58 KB, two)
+    {MS, 1, 4, 4, 0, 2}, {MS, 2, 2, 8, 0, 2}, {MS, 1, 4, 4, 1, 2}, {MS, 2, 2, 8, 1, 2}, {MS, 1, 4, 4, 2, 2}, {MS, 2, 2, 4, 2, 2},
 };
 constexpr int WG_NROWS = sizeof(WG_ROWS) / sizeof(WG_ROWS[0]);
 
@@ -969,10 +964,9 @@ constexpr WgRowInfo wg_row_info() {
     constexpr WgRow r = WG_ROWS[I];
     using Cfg = WgCfg<r.a_t, r.b_t, (r.mode == TNR_CONV_4x4_S2 ? 4 : 9)>;
     constexpr size_t lds = wg_lds_bytes(r, Cfg::KS, Cfg::WPG, Cfg::J);
-    // WgCfg picks the workgroups per CU, except for the half-height TNR_MMA_BF16X3 classes.  Two workgroups per CU share the 160 KB; a
-    // TNR_MMA_BF16X3 class inherited from the fp32 plan may exceed 80 KB: the LDS then limits it to one workgroup per CU.
+    // WgCfg picks the workgroups per CU, except for the half-height TNR_MMA_BF16X3 classes.  Two workgroups per CU share the 160 KB.
     static_assert(r.wps == Cfg::WAVES_PER_SIMD || (r.bf == 2 && !r.db), "workgroups per CU differ from WgCfg's");
-    static_assert(lds <= ((r.wps == 1 || r.bf == 2) ? 160 : 80) * 1024, "wgrad tile exceeds the LDS budget of its occupancy regime");
+    static_assert(lds <= (r.wps == 1 ? 160 : 80) * 1024, "wgrad tile exceeds the LDS budget of its occupancy regime");
     return {Cfg::KS, lds};
 }
 template <int... I>
@@ -988,35 +982,35 @@ struct WgPlan {
     int64_t ws_floats, db_floats;
 };
 
-// The tile class of one layer, decided top-down: the first rule that matches names the class.  x3_occ: TNR_WG_X3_OCC.
-WgRow wgrad_class(const tnr_wgrad_desc *d, int x3_occ) {
+// The tile class of one layer, decided top-down: the first rule that matches names the class.
+WgRow wgrad_class(const tnr_wgrad_desc *d) {
     const int m = d->mode, bf = d->mma;
     const bool wide = d->Cout > 32;
     const int cin_blocks = tnr_cdiv(d->Cin, 32);
     if (m == TNR_CONV_4x4_S2) {                  // 4 * cin_blocks virtual blocks: always a full 128- or 64-wide job
         if (!wide) return {m, 1, 4, 4, bf, 2};
-        return {m, 2, 2, (bf == TNR_MMA_BF16X3 && x3_occ >= 2) ? 4 : 8, bf, 2};
+        return {m, 2, 2, bf == TNR_MMA_BF16X3 ? 4 : 8, bf, 2};
     }
     if (!wide && (cin_blocks == 3 || cin_blocks == 5)) return {m, 1, 3, 4, bf, 2};      // (the caller normally splits 160 = 96 + 64 itself)
     const int a_t = wide ? 2 : 1;
-    if (bf == TNR_MMA_BF16X3 && x3_occ >= 2) {
+    if (bf == TNR_MMA_BF16X3) {
         // half-height tiles of at most 64 input channels (32 x 128 jobs become two 32 x 64 jobs: the 128-wide halo tile alone is 95 KB):
         // <= 66 KB of pre-split LDS image per tile set, >= 2 tile rows per pixel group
         const int b_t = cin_blocks >= 2 ? 2 : 1, thg = a_t * b_t == 1 ? 8 : 4;
-        const bool pipelined = x3_occ == 3 && m == TNR_CONV_3x3 && d->pad_mode == 0 &&
+        const bool pipelined = m == TNR_CONV_3x3 && d->pad_mode == 0 &&
                                (int64_t)d->N * d->H * d->W * d->x.ctot < (1LL << 30) && (int64_t)d->N * d->Ho * d->Wo * d->g.ctot < (1LL << 30);
         return {m, a_t, b_t, thg, bf, pipelined ? 1 : 2, pipelined};
     }
     if (wide) return cin_blocks >= 2 ? WgRow{m, 2, 2, 8, bf, 1} : WgRow{m, 2, 1, 16, bf, 1};
     if (cin_blocks == 1) return {m, 1, 1, 16, bf, 1};
-    if (cin_blocks == 2) return {m, 1, 2, bf == TNR_MMA_BF16X3 ? 8 : 16, bf, 1};
+    if (cin_blocks == 2) return {m, 1, 2, 16, bf, 1};
     return {m, 1, 4, 8, bf, 1};
 }
 
 // Tile class and slab geometry of one layer; the split count is chosen for `group_jobs` (cin block, cout block) pairs sharing the launch
 // (0: this layer alone).  The geometry is filled in either way; a class outside the table (p.row = -1) is TNR_EINVAL.
-int plan_wgrad(const tnr_wgrad_desc *d, int group_jobs, int x3_occ, WgPlan &p) {
-    const WgRow c = wgrad_class(d, x3_occ);
+int plan_wgrad(const tnr_wgrad_desc *d, int group_jobs, WgPlan &p) {
+    const WgRow c = wgrad_class(d);
     p.row = -1;
     for (int i = 0; i < WG_NROWS; ++i)
         if (WG_ROWS[i] == c) p.row = i;
@@ -1040,13 +1034,8 @@ int plan_wgrad(const tnr_wgrad_desc *d, int group_jobs, int x3_occ, WgPlan &p) {
     p.splits = tnr_cdiv(p.tiles_total, p.tiles_per_split);
     p.ws_floats = (int64_t)p.splits * p.ntaps * p.KoutP * p.KinVP;
     p.db_floats = (int64_t)p.splits * p.KoutP;
-    TNR_REQUIRE(p.row >= 0, "wgrad: no tile class for %d -> %d channels in mode %d (mma %d, TNR_WG_X3_OCC=%d)", d->Cin, d->Cout, d->mode, d->mma, x3_occ);
+    TNR_REQUIRE(p.row >= 0, "wgrad: no tile class for %d -> %d channels in mode %d (mma %d)", d->Cin, d->Cout, d->mode, d->mma);
     return TNR_OK;
-}
-
-int wgrad_x3_occ() {          // TNR_MMA_BF16X3: 1 the fp32 classes, 2 half-height tiles and two workgroups per CU, 3 also the pipelined form
-    static const int v = [] { const char *e = getenv("TNR_WG_X3_OCC"); return e ? atoi(e) : 3; }();
-    return v;
 }
 
 template <int I>
@@ -1091,14 +1080,14 @@ int check_wgrad_desc(const tnr_wgrad_desc *d) {
 extern "C" int64_t tnr_wgrad_workspace_bytes(const tnr_wgrad_desc *d) {
     if (d == nullptr) return 0;
     WgPlan p;
-    plan_wgrad(d, 0, wgrad_x3_occ(), p);   // a layer alone uses the most splits: this bound also covers any group
+    plan_wgrad(d, 0, p);   // a layer alone uses the most splits: this bound also covers any group
     return (p.ws_floats + p.db_floats) * (int64_t)sizeof(float);
 }
 
-extern "C" int tnr_wgrad_tile_class(const tnr_wgrad_desc *d, int32_t group_jobs, int32_t x3_occ, int32_t out[12]) {
+extern "C" int tnr_wgrad_tile_class(const tnr_wgrad_desc *d, int32_t group_jobs, int32_t out[12]) {
     TNR_REQUIRE(d != nullptr && out != nullptr, "wgrad_tile_class: null pointer");
     WgPlan p;
-    if (const int rc = plan_wgrad(d, group_jobs, x3_occ < 0 ? wgrad_x3_occ() : x3_occ, p)) return rc;
+    if (const int rc = plan_wgrad(d, group_jobs, p)) return rc;
     const WgRow &r = WG_ROWS[p.row];
     const int32_t v[12] = {r.mode, r.a_t, r.b_t, r.thg, r.bf, r.wps, r.db, WG_INFO[p.row].ks, p.splits, p.tiles_per_split, (int32_t)WG_INFO[p.row].lds, p.row};
     for (int i = 0; i < 12; ++i) out[i] = v[i];
@@ -1108,14 +1097,13 @@ extern "C" int tnr_wgrad_tile_class(const tnr_wgrad_desc *d, int32_t group_jobs,
 extern "C" int tnr_conv_wgrad_group(const tnr_wgrad_desc *descs, int32_t n, void *stream) {
     TNR_REQUIRE(descs != nullptr && n >= 1 && n <= TNR_WGRAD_GROUP_MAX, "wgrad_group: 1..%d layers per group", TNR_WGRAD_GROUP_MAX);
     const tnr_wgrad_desc &d0 = descs[0];
-    const int x3_occ = wgrad_x3_occ();
     WgPlan plans[TNR_WGRAD_GROUP_MAX];
     int jobs = 0;
     for (int i = 0; i < n; ++i) {
         const tnr_wgrad_desc &di = descs[i];
         if (const int rc = check_wgrad_desc(&di)) return rc;
         TNR_REQUIRE(di.mma >= TNR_MMA_F32 && di.mma <= TNR_MMA_BF16X3, "wgrad: bad mma %d", di.mma);
-        if (const int rc = plan_wgrad(&di, 0, x3_occ, plans[i])) return rc;
+        if (const int rc = plan_wgrad(&di, 0, plans[i])) return rc;
         jobs += plans[i].ncib * plans[i].ncob;
         TNR_REQUIRE(di.mode == d0.mode && di.N == d0.N && di.H == d0.H && di.W == d0.W && di.Ho == d0.Ho && di.Wo == d0.Wo,
                     "wgrad_group: layer %d does not share the pixel geometry of layer 0", i);
@@ -1127,12 +1115,11 @@ extern "C" int tnr_conv_wgrad_group(const tnr_wgrad_desc *descs, int32_t n, void
     TNR_REQUIRE(jobs <= 65535, "wgrad_group: too many channel blocks");
     TNR_REQUIRE(d0.pad_mode == 0 || (d0.pad_mode == 1 && d0.mode == TNR_CONV_3x3 && d0.H >= 2 && d0.W >= 2), "wgrad: pad_mode 1 (reflection) is for TNR_CONV_3x3");
     if (n > 1)                                   // the split count of the whole group's jobs
-        for (int i = 0; i < n; ++i) plan_wgrad(&descs[i], jobs, x3_occ, plans[i]);
+        for (int i = 0; i < n; ++i) plan_wgrad(&descs[i], jobs, plans[i]);
     const WgPlan &p0 = plans[0];
     WgK k;
     RedK r;
-    static const int red_rpb = [] { const char *e = getenv("TNR_WGRAD_REDUCE_RPB"); return e ? atoi(e) : 8; }();      // (A/B switch: 1 = a block per row always)
-    const int rpb = (red_rpb == 8 && p0.splits <= 32) ? 8 : 1;
+    const int rpb = p0.splits <= 32 ? 8 : 1;
     int job_begin = 0, blk_begin = 0;
     for (int i = 0; i < n; ++i) {
         const tnr_wgrad_desc *d = &descs[i];

@@ -1101,8 +1101,6 @@ def conv_col(x, wp_col, y, k, stride=1, pad=1, **epi):
 
 
 WGRAD_GROUP_MAX = 12
-WGRAD_PAIR = os.environ.get("TNR_WGRAD_PAIR", "1") != "0"   # dense blocks: conv4+conv3 and conv2+conv1 as 64-cout pairs (A/B switch)
-WGRAD_X3 = os.environ.get("TNR_WGRAD_X3", "1") == "1"   # TNR_MMA=bf16x3 also in the weight-gradient kernel (A/B switch)
 
 
 def _wgrad_desc(d, x, g, dw, db, mode, cin_begin, alpha, beta, reflect=False, pair=None):
@@ -1114,7 +1112,7 @@ def _wgrad_desc(d, x, g, dw, db, mode, cin_begin, alpha, beta, reflect=False, pa
     d.dw, d.cin_total, d.cin_begin = dw.data_ptr(), dw.shape[1], cin_begin
     d.db = hip.ptr(db)
     d.alpha, d.beta = alpha, beta
-    d.mma = hip.MMA_F32 if (MMA == hip.MMA_BF16X3 and not WGRAD_X3) else MMA
+    d.mma = MMA
     d.pad_mode = 1 if reflect else 0
     if pair is not None:           # cout pair: g covers two layers' gradients, channels >= split belong to (dw2, db2)
         dw2, db2, split = pair
@@ -1153,11 +1151,11 @@ def wgrad_group(items, mode=CONV_3x3, family=None):
     PROFILE.end(family or "wgrad_tile", flops, t0, (sum(it["x"].C for it in items) if n > 1 else x0.C, g0.C, g0.H, mode + 100 * (n - 1)))
 
 
-def wgrad_tile_class(desc, group_jobs=0, x3_occ=-1):
+def wgrad_tile_class(desc, group_jobs=0):
     """tnr_wgrad_tile_class of a WgradDesc (host only, no launch) -> dict of the kernel's template arguments mode / a_t / b_t / thg / bf / wps /
     db and ks, splits, tiles_per_split, lds, row (the index in the library's table of tile classes)."""
     out = (C.c_int32 * 12)()
-    hip.check(hip.load().tnr_wgrad_tile_class(C.byref(desc), group_jobs, x3_occ, C.byref(out)), "wgrad_tile_class")
+    hip.check(hip.load().tnr_wgrad_tile_class(C.byref(desc), group_jobs, C.byref(out)), "wgrad_tile_class")
     return dict(zip(("mode", "a_t", "b_t", "thg", "bf", "wps", "db", "ks", "splits", "tiles_per_split", "lds", "row"), out))
 
 
