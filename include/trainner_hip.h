@@ -225,6 +225,14 @@ int tnr_upconv_wgrad_unfold(const float *dws, float *dw3, int32_t Cout, int32_t 
 int tnr_pack_dense_dims(int32_t nf, int32_t gc, int32_t t, int32_t *KoutP, int32_t *KinP, int64_t *n_out);
 int tnr_pack_dense_dgrad(const tnr_dense_pack_item *items_dev, int32_t n, int64_t max_out, void *stream);
 int tnr_conv_forward(const tnr_conv_desc *d, void *stream);
+/* Host-only query (no device, no launch, no memory behind the descriptor's pointers is read): what tnr_conv_forward launches for the
+ * descriptor AS IT STANDS -- wq / wq_form / ws / shuffle set or not --, through the code the entry itself decides by.  out[0] the kernel
+ * (0 conv_tile, 1 conv3x3_x3w8, 2 conv3x3_d4, 3 conv_s2_d4, 4 conv3x3_wino); out[1..4] tw, th, nt (output channels per workgroup / 32),
+ * mt (32-pixel M-tiles per wave; 0: the Winograd kernel has none); out[5..8] tiles_x, tiles_y, ncb, tiles (split-K: every split counted;
+ * the stride-2 data-gradient: its four parity classes counted); out[9] ksplit; out[10] the persistent grid's cap in workgroups per CU
+ * (the launch has min(tiles, cap x CUs) workgroups; 0: one workgroup per tile); out[11] 0.  A descriptor the entry refuses is refused
+ * here with the same message (its check for null x / y / wp apart).                                   */
+int tnr_conv_launch_class(const tnr_conv_desc *d, int32_t out[12]);
 /* dst[p][c] = (src ? src[p][c] : 1) * (1 + sigma * n(key0, key1, (pix0 + p) * C / 4 + c / 4)) for `pixels` pixels of C channels: the
  * multiplier field of tnr_conv_desc.noise_* on a plain NHWC tensor (dst may alias src).  Used where the gradient of a noised tensor
  * is needed next to the plain one (the RRDB skip, RRDBNet_arch.py:96), and by tests to read the engine's draw.  C % 4 == 0.          */

@@ -2,6 +2,8 @@
 same op (F.conv2d + autograd, F.batch_norm, ...), on shapes that exercise ragged tiles, channel
 windows of wider buffers (the dense-block layout), 3/4-channel images and every conv geometry.
 Tolerance: fp32 round-off only -- max |err| <= 2e-5 * (max |ref| + 1) unless stated.
+The edge shapes of the forward and data-gradient convolutions (one pixel, lines, ragged tiles, thresholds between kernels, the second
+trip of a persistent grid, uneven split-K) run against fp64 in test_gpu_conv_edges.py.
 """
 import math
 

@@ -4,6 +4,15 @@
 #include "common.h"
 #include "gauss_noise.h"
 
+// What a weight-stream launcher decided for a descriptor, without launching (tnr_plan_conv3x3_d4, tnr_plan_conv_s2_d4,
+// tnr_plan_conv3x3_wino; tnr_conv_forward and tnr_conv_launch_class read it): the tile, the grid stream_k_from_desc laid out and the
+// workgroups per CU the persistent grid is capped at.  (Outside the namespace below: it crosses translation units.)
+struct ConvStreamPlan {
+    int tw, th, nt, mt;
+    int tiles_x, tiles_y, ncb, tiles;
+    int cap;
+};
+
 namespace {
 
 typedef unsigned tnr_u32x4 __attribute__((ext_vector_type(4)));
@@ -172,6 +181,13 @@ bool stream_k_from_desc(StreamK &c, const tnr_conv_desc &d, int64_t wq_bytes, in
     const int64_t tiles = (int64_t)c.tiles_x * c.tiles_y * c.ncb * d.N * par;
     c.tiles = (int)tiles;
     return tiles < (1LL << 31);
+}
+
+template <class StreamK>
+inline void stream_plan_of(const StreamK &c, int tw, int th, int nt, int mt, int cap, ConvStreamPlan *p) {
+    p->tw = tw; p->th = th; p->nt = nt; p->mt = mt;
+    p->tiles_x = c.tiles_x; p->tiles_y = c.tiles_y; p->ncb = c.ncb; p->tiles = c.tiles;
+    p->cap = cap;
 }
 
 // x, y and the optional r1 / r2 / mask views (with r1_ch and the mask's channel range) start and stride on 4-channel boundaries

@@ -1185,17 +1185,48 @@ extern "C" int tnr_conv_wq_pack(const tnr_conv_desc *d, void *image, int64_t ima
     return tnr_check_launch("conv_wq_pack");
 }
 
+namespace {
+
+constexpr int SW_GRID_CAP = 2;      // persistent grids of the weight-stream kernels: at most this many workgroups per CU
+
+// Does the four-tap kernel take this launch?  Fills its arguments: the launcher's and the plan query's one answer.
+bool s2_takes(const tnr_conv_desc *d, S2K &c) {
+    if (!s2_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wq_bytes(d) || d->noise_pos != 0) return false;
+    return stream_k_from_desc(c, *d, tnr_conv_wq_bytes(d), SW_TW, SW_TH, d->mode == TNR_DGRAD_4x4_S2 ? 4 : 1);
+}
+
+// The same for the direct 3x3 kernel.
+bool d4_takes(const tnr_conv_desc *d, D4K &c) {
+    if (!d4_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wq_bytes(d) || d->noise_pos < 0 || d->noise_pos > 2) return false;
+    return stream_k_from_desc(c, *d, tnr_conv_wq_bytes(d), SW_TW, SW_TH, 1);
+}
+
+}  // namespace
+
+// host only (no device, no launch): 0 and the plan where tnr_launch_conv_s2_d4 / tnr_launch_conv3x3_d4 would launch, 1 where they decline
+int tnr_plan_conv_s2_d4(const tnr_conv_desc *d, ConvStreamPlan *p) {
+    S2K c;
+    if (!s2_takes(d, c)) return 1;
+    stream_plan_of(c, SW_TW, SW_TH, 2, 2, SW_GRID_CAP, p);
+    return 0;
+}
+int tnr_plan_conv3x3_d4(const tnr_conv_desc *d, ConvStreamPlan *p) {
+    D4K c;
+    if (!d4_takes(d, c)) return 1;
+    stream_plan_of(c, SW_TW, SW_TH, 2, 2, SW_GRID_CAP, p);
+    return 0;
+}
+
 // the four-tap forms (4x4 stride 2 forward, its data-gradient) with a pre-split weight stream; 1: not for this kernel
 int tnr_launch_conv_s2_d4(const tnr_conv_desc *d, void *stream) {
-    if (!s2_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wq_bytes(d) || d->noise_pos != 0) return 1;
+    S2K c;
+    if (!s2_takes(d, c)) return 1;
     static int cus = 0;
     if (const int rc = tnr_kernel_setup(&cus, "conv_s2_d4", {{conv_s2_d4_kernel<TNR_CONV_4x4_S2, false>, SW_LDS_BYTES}, {conv_s2_d4_kernel<TNR_CONV_4x4_S2, true>, SW_LDS_BYTES},
                                                              {conv_s2_d4_kernel<TNR_DGRAD_4x4_S2, false>, SW_LDS_BYTES}, {conv_s2_d4_kernel<TNR_DGRAD_4x4_S2, true>, SW_LDS_BYTES}}))
         return rc;
     const bool dg = d->mode == TNR_DGRAD_4x4_S2;
-    S2K c;
-    if (!stream_k_from_desc(c, *d, tnr_conv_wq_bytes(d), SW_TW, SW_TH, dg ? 4 : 1)) return 1;
-    const unsigned grid = (unsigned)(c.tiles < 2 * cus ? c.tiles : 2 * cus);
+    const unsigned grid = (unsigned)(c.tiles < SW_GRID_CAP * cus ? c.tiles : SW_GRID_CAP * cus);
     const bool amp = d->mma == TNR_MMA_BF16;
     if (dg) {
         if (amp) hipLaunchKernelGGL((conv_s2_d4_kernel<TNR_DGRAD_4x4_S2, true>), dim3(grid), dim3(256), SW_LDS_BYTES, (hipStream_t)stream, c);
@@ -1209,14 +1240,13 @@ int tnr_launch_conv_s2_d4(const tnr_conv_desc *d, void *stream) {
 
 // called by tnr_conv_forward (conv_tile.hip) for a launch that carries a pre-split weight stream; 1: not for this kernel
 int tnr_launch_conv3x3_d4(const tnr_conv_desc *d, void *stream) {
-    if (!d4_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wq_bytes(d) || d->noise_pos < 0 || d->noise_pos > 2) return 1;
+    D4K c;
+    if (!d4_takes(d, c)) return 1;
     static int cus = 0;
     if (const int rc = tnr_kernel_setup(&cus, "conv3x3_d4", {{conv3x3_d4_kernel<>, SW_LDS_BYTES}, {conv3x3_d4_kernel<true>, SW_LDS_BYTES},
                                                              {conv3x3_d4_kernel<false, true>, SW_LDS_BYTES}, {conv3x3_d4_kernel<true, true>, SW_LDS_BYTES}}))
         return rc;
-    D4K c;
-    if (!stream_k_from_desc(c, *d, tnr_conv_wq_bytes(d), SW_TW, SW_TH, 1)) return 1;
-    const unsigned grid = (unsigned)(c.tiles < 2 * cus ? c.tiles : 2 * cus);
+    const unsigned grid = (unsigned)(c.tiles < SW_GRID_CAP * cus ? c.tiles : SW_GRID_CAP * cus);
     if (d->shuffle == 2) {
         // the buffer the store addresses is the shuffled one: [N, 2 Ho, 2 Wo, Cout / 4] (same element count)
         if (d->mma == TNR_MMA_BF16) hipLaunchKernelGGL((conv3x3_d4_kernel<true, true>), dim3(grid), dim3(256), SW_LDS_BYTES, (hipStream_t)stream, c);

@@ -169,9 +169,32 @@ int conv_ksplit(const tnr_conv_desc *d, int64_t tiles) {
 int tnr_launch_conv3x3_d4(const tnr_conv_desc *d, void *stream);      // conv_sweep.hip (1: not for that kernel)
 int tnr_launch_conv3x3_wino(const tnr_conv_desc *d, void *stream);    // conv_wino.hip (1: not for that kernel)
 int tnr_launch_conv_s2_d4(const tnr_conv_desc *d, void *stream);      // conv_sweep.hip: the four-tap forms (1: not for that kernel)
+int tnr_plan_conv3x3_d4(const tnr_conv_desc *d, ConvStreamPlan *p);   // the launchers' own answers without the launch (0: takes it, 1: declines)
+int tnr_plan_conv3x3_wino(const tnr_conv_desc *d, ConvStreamPlan *p);
+int tnr_plan_conv_s2_d4(const tnr_conv_desc *d, ConvStreamPlan *p);
 
-extern "C" int tnr_conv_forward(const tnr_conv_desc *d, void *stream) {
-    TNR_REQUIRE(d != nullptr && d->x.ptr && d->y.ptr && d->wp, "conv: null pointer");
+namespace {
+
+enum ConvKernel { CONV_K_TILE = 0, CONV_K_X3W8 = 1, CONV_K_D4 = 2, CONV_K_S2_D4 = 3, CONV_K_WINO = 4 };
+
+// What tnr_conv_forward does with a descriptor, decided in ONE place for the entry and for tnr_conv_launch_class: the kernel, its tile
+// and grid, the split-K factor, and for the kernels of this file their arguments (k: the split-K rewrite applied; red: the reduce
+// launch's).  Host only.  `launching`: the entry's null-pointer check (the query describes a descriptor that may have no memory
+// behind it).
+struct ConvLaunch {
+    int kernel;
+    int tw, th, nt, mt;
+    int tiles_x, tiles_y, ncb;
+    int64_t tiles;      // workgroup tiles of the launch (split-K: every split counted)
+    int ksplit;
+    int cap;            // persistent grid: min(tiles, cap x CUs) workgroups; 0: one workgroup per tile
+    ConvK k;
+    SplitRedK red;
+};
+
+int conv_decide(const tnr_conv_desc *d, bool launching, ConvLaunch &L) {
+    TNR_REQUIRE(d != nullptr, "conv: null pointer");
+    if (launching) TNR_REQUIRE(d->x.ptr && d->y.ptr && d->wp, "conv: null pointer");
     TNR_REQUIRE(d->mode >= TNR_CONV_3x3 && d->mode <= TNR_CONV_7x7_C4, "conv: bad mode %d", d->mode);
     if (d->mode == TNR_CONV_3x3_C4)
         TNR_REQUIRE(d->x.ctot == 4 && d->x.coff == 0 && d->Cin == 4 && d->KinP == 48, "conv3x3_c4: needs an NHWC4 input view and a C4 packing");
@@ -205,20 +228,18 @@ extern "C" int tnr_conv_forward(const tnr_conv_desc *d, void *stream) {
             TNR_REQUIRE(d->Ho == 2 * d->H && d->Wo == 2 * d->W, "dgrad4x4s2: output must be 2x gout size");
             break;
     }
-    ConvK k = conv_k_from_desc(*d);
+    ConvK &k = L.k = conv_k_from_desc(*d);
     const ConvTileGeom g = conv_tile_geom(d);
-    const int tw = g.tw, nt = g.nt, sh = k.th_space;
-    const bool big_m = g.big_m;
+    const int sh = k.th_space;
     k.tiles_x = g.tiles_x; k.tiles_y = g.tiles_y; k.ncb = g.ncb;
     int64_t tiles = g.tiles;
     TNR_REQUIRE(tiles > 0 && tiles < (1LL << 31), "conv: grid too large");
-    hipStream_t s = (hipStream_t)stream;
     // split-K for launches that cannot fill the chip (see tnr_conv_workspace_bytes)
     const int ksplit = conv_ksplit(d, tiles);
     TNR_REQUIRE(d->mma >= TNR_MMA_F32 && d->mma <= TNR_MMA_BF16X3, "conv: bad mma %d", d->mma);
     TNR_REQUIRE(d->pad_mode == 0 || (d->pad_mode == 1 && d->mode == TNR_CONV_3x3 && d->H >= 2 && d->W >= 2) ||
                 (d->pad_mode == 1 && d->mode == TNR_CONV_7x7_C4 && d->H >= 4 && d->W >= 4), "conv: pad_mode 1 (reflection) is for TNR_CONV_3x3 and TNR_CONV_7x7_C4");
-    SplitRedK red;
+    SplitRedK &red = L.red = SplitRedK{};
     if (ksplit > 1 && d->ws != nullptr) {
         const int64_t plane = (int64_t)d->N * d->Ho * d->Wo * k.KoutP;
         TNR_REQUIRE(plane * ksplit * (int64_t)sizeof(float) <= d->ws_bytes, "conv: split-K workspace too small");
@@ -231,44 +252,98 @@ extern "C" int tnr_conv_forward(const tnr_conv_desc *d, void *stream) {
         k.ksplit = ksplit; k.split_stride = (size_t)plane;
         tiles *= ksplit;
     }
-    int rc;
+    L.ksplit = k.ksplit;
+    ConvStreamPlan p;
+    auto stream_kernel = [&](int kernel) {
+        L.kernel = kernel;
+        L.tw = p.tw; L.th = p.th; L.nt = p.nt; L.mt = p.mt;
+        L.tiles_x = p.tiles_x; L.tiles_y = p.tiles_y; L.ncb = p.ncb; L.tiles = p.tiles; L.cap = p.cap;
+        return TNR_OK;
+    };
     if (d->wq != nullptr && d->wq_form == 1) {     // transform-domain weight stream: the Winograd F(2x2, 3x3) kernel (conv_wino.hip) or nothing
         TNR_REQUIRE(k.ksplit == 1, "conv: a Winograd weight stream cannot be combined with a split-K workspace");
-        rc = tnr_launch_conv3x3_wino(d, (void *)s);
-        TNR_REQUIRE(rc != 1, "conv: wq_form = 1 but the launch does not qualify for the Winograd kernel (tnr_conv_wino_bytes() == 0)");
-        return rc;
+        TNR_REQUIRE(tnr_plan_conv3x3_wino(d, &p) == 0, "conv: wq_form = 1 but the launch does not qualify for the Winograd kernel (tnr_conv_wino_bytes() == 0)");
+        return stream_kernel(CONV_K_WINO);
     }
     if (d->wq != nullptr && k.ksplit == 1) {       // pre-split weight stream: the direct four-wave kernel (conv_sweep.hip), when the launch qualifies
         static const bool d4 = [] { const char *e = std::getenv("TNR_X3_D4"); return e == nullptr || e[0] != '0'; }();
         if (d4 || d->shuffle != 0) {
-            rc = (d->mode == TNR_CONV_4x4_S2 || d->mode == TNR_DGRAD_4x4_S2) ? tnr_launch_conv_s2_d4(d, (void *)s) : tnr_launch_conv3x3_d4(d, (void *)s);
-            if (rc <= 0) return rc;
+            const bool four_tap = d->mode == TNR_CONV_4x4_S2 || d->mode == TNR_DGRAD_4x4_S2;
+            if ((four_tap ? tnr_plan_conv_s2_d4(d, &p) : tnr_plan_conv3x3_d4(d, &p)) == 0) return stream_kernel(four_tap ? CONV_K_S2_D4 : CONV_K_D4);
         }
     }
     TNR_REQUIRE(d->shuffle == 0, "conv: a pixel-shuffle store (shuffle = %d) exists in the weight-stream kernel only (tnr_conv_wq_bytes() == 0 for this launch)", d->shuffle);
+    L.cap = 0;
     {   // TNR_MMA_BF16X3, 64-cout 3x3 layers: the 8-wave kernel with both operands pre-split in LDS (conv_x3w8.h; TNR_X3_W8=0: off)
         static const bool w8 = [] { const char *e = std::getenv("TNR_X3_W8"); return e == nullptr || e[0] != '0'; }();
-        if (w8 && d->mode == TNR_CONV_3x3 && nt == 2 && tw == 32 && sh >= 16 && conv3x3_x3w8_ok(k)) return launch_conv3x3_x3w8(k, s);
+        if (w8 && d->mode == TNR_CONV_3x3 && g.nt == 2 && g.tw == 32 && sh >= 16 && conv3x3_x3w8_ok(k)) {
+            using G = X3W8;
+            L.kernel = CONV_K_X3W8;
+            L.tw = G::TW; L.th = G::TH; L.nt = G::NT; L.mt = G::MT;
+            conv3x3_x3w8_grid(k);
+            L.tiles_x = k.tiles_x; L.tiles_y = k.tiles_y; L.ncb = k.ncb;
+            L.tiles = (int64_t)k.tiles_x * k.tiles_y * k.ncb * k.N;
+            return TNR_OK;
+        }
     }
-    if (big_m) {
-        rc = launch_conv<TNR_CONV_3x3, 32, 1, 4>(k, (int)tiles, s);
+    L.kernel = CONV_K_TILE;
+    L.tw = g.tw; L.th = g.th; L.nt = g.nt; L.mt = g.big_m ? 4 : 2;
+    L.tiles_x = g.tiles_x; L.tiles_y = g.tiles_y; L.ncb = g.ncb; L.tiles = tiles;
+    return TNR_OK;
+}
+
+}  // namespace
+
+extern "C" int tnr_conv_forward(const tnr_conv_desc *d, void *stream) {
+    ConvLaunch L;
+    if (const int rc = conv_decide(d, true, L)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const ConvK &k = L.k;
+    int rc;
+    switch (L.kernel) {
+        case CONV_K_WINO: rc = tnr_launch_conv3x3_wino(d, (void *)s); break;
+        case CONV_K_D4: rc = tnr_launch_conv3x3_d4(d, (void *)s); break;
+        case CONV_K_S2_D4: rc = tnr_launch_conv_s2_d4(d, (void *)s); break;
+        case CONV_K_X3W8: return launch_conv3x3_x3w8(k, s);
+        default: rc = 1; break;
+    }
+    if (L.kernel != CONV_K_TILE) {
+        TNR_REQUIRE(rc != 1, "conv: the weight-stream launcher declined a launch its own plan had taken");
+        return rc;
+    }
+    const int tiles = (int)L.tiles;
+    if (L.mt == 4) {
+        rc = launch_conv<TNR_CONV_3x3, 32, 1, 4>(k, tiles, s);
     } else {
         switch (d->mode) {
-            case TNR_CONV_3x3: rc = dispatch_conv<TNR_CONV_3x3>(k, tw, nt, (int)tiles, s); break;
-            case TNR_CONV_3x3_UP2: rc = dispatch_conv<TNR_CONV_3x3_UP2>(k, tw, nt, (int)tiles, s); break;
-            case TNR_CONV_4x4_S2: rc = dispatch_conv<TNR_CONV_4x4_S2>(k, tw, nt, (int)tiles, s); break;
-            case TNR_CONV_1x1: rc = dispatch_conv<TNR_CONV_1x1>(k, tw, nt, (int)tiles, s); break;
-            case TNR_CONV_3x3_C4: rc = dispatch_conv<TNR_CONV_3x3_C4>(k, tw, nt, (int)tiles, s); break;
-            case TNR_CONV_7x7_C4: rc = dispatch_conv<TNR_CONV_7x7_C4>(k, tw, nt, (int)tiles, s); break;
-            default: rc = dispatch_conv<TNR_DGRAD_4x4_S2>(k, tw, nt, (int)tiles, s); break;
+            case TNR_CONV_3x3: rc = dispatch_conv<TNR_CONV_3x3>(k, L.tw, L.nt, tiles, s); break;
+            case TNR_CONV_3x3_UP2: rc = dispatch_conv<TNR_CONV_3x3_UP2>(k, L.tw, L.nt, tiles, s); break;
+            case TNR_CONV_4x4_S2: rc = dispatch_conv<TNR_CONV_4x4_S2>(k, L.tw, L.nt, tiles, s); break;
+            case TNR_CONV_1x1: rc = dispatch_conv<TNR_CONV_1x1>(k, L.tw, L.nt, tiles, s); break;
+            case TNR_CONV_3x3_C4: rc = dispatch_conv<TNR_CONV_3x3_C4>(k, L.tw, L.nt, tiles, s); break;
+            case TNR_CONV_7x7_C4: rc = dispatch_conv<TNR_CONV_7x7_C4>(k, L.tw, L.nt, tiles, s); break;
+            default: rc = dispatch_conv<TNR_DGRAD_4x4_S2>(k, L.tw, L.nt, tiles, s); break;
         }
     }
     if (rc != TNR_OK || k.ksplit == 1) return rc;
+    const SplitRedK &red = L.red;
     const long long work = red.pixels * (red.CoutP >> 2);
     long long blocks = (work + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, red);
     return tnr_check_launch("conv_splitk_reduce");
+}
+
+// Host-only query (no device, no launch): what tnr_conv_forward would launch for the descriptor as it stands.
+// out: kernel (0 conv_tile, 1 conv3x3_x3w8, 2 conv3x3_d4, 3 conv_s2_d4, 4 conv3x3_wino), tw, th, nt, mt, tiles_x, tiles_y, ncb, tiles, ksplit,
+// grid cap in workgroups per CU (0: none), 0.
+extern "C" int tnr_conv_launch_class(const tnr_conv_desc *d, int32_t out[12]) {
+    TNR_REQUIRE(d != nullptr && out != nullptr, "conv_launch_class: null pointer");
+    ConvLaunch L;
+    if (const int rc = conv_decide(d, false, L)) return rc;
+    const int32_t v[12] = {L.kernel, L.tw, L.th, L.nt, L.mt, L.tiles_x, L.tiles_y, L.ncb, (int32_t)L.tiles, L.ksplit, L.cap, 0};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return TNR_OK;
 }
 
 extern "C" int64_t tnr_conv_workspace_bytes(const tnr_conv_desc *d) {

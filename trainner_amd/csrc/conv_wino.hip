@@ -553,21 +553,36 @@ extern "C" int tnr_conv_wino_pack(const tnr_conv_desc *d, void *image, int64_t i
 
 namespace {
 
+constexpr int WN_GRID_CAP = 1;      // the persistent grid: at most one workgroup per CU
+
+// Does the Winograd kernel take this launch?  Fills its arguments: the launcher's and the plan query's one answer.
+bool wino_takes(const tnr_conv_desc *d, WinoK &c) {
+    if (!wino_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wino_bytes(d) || d->noise_pos < 0 || d->noise_pos > 2) return false;
+    return stream_k_from_desc(c, *d, tnr_conv_wino_bytes(d), WN_T, WN_T, 1);
+}
+
 // pool: 0 = the plain store, 2 = the pooled one (d->y the [N, Ho / 2, Wo / 2] view, route optional); 1: not for this kernel
 int launch_wino(const tnr_conv_desc *d, int pool, unsigned char *route, void *stream) {
-    if (!wino_ok(d) || d->wq == nullptr || d->wq_bytes < tnr_conv_wino_bytes(d) || d->noise_pos < 0 || d->noise_pos > 2) return 1;
+    WinoK c;
+    if (!wino_takes(d, c)) return 1;
     static int cus = 0;
     if (const int rc = tnr_kernel_setup(&cus, "conv3x3_wino", {{conv3x3_wino_kernel, WN_LDS_BYTES}})) return rc;
-    WinoK c;
-    if (!stream_k_from_desc(c, *d, tnr_conv_wino_bytes(d), WN_T, WN_T, 1)) return 1;
     c.pool = pool;
     c.route = route;
-    const int grid = c.tiles < cus ? c.tiles : cus;
+    const int grid = c.tiles < WN_GRID_CAP * cus ? c.tiles : WN_GRID_CAP * cus;
     hipLaunchKernelGGL(conv3x3_wino_kernel, dim3((unsigned)grid), dim3(512), WN_LDS_BYTES, (hipStream_t)stream, c);
     return tnr_check_launch("conv3x3_wino");
 }
 
 }  // namespace
+
+// host only (no device, no launch): 0 and the plan where tnr_launch_conv3x3_wino would launch, 1 where it declines
+int tnr_plan_conv3x3_wino(const tnr_conv_desc *d, ConvStreamPlan *p) {
+    WinoK c;
+    if (!wino_takes(d, c)) return 1;
+    stream_plan_of(c, WN_T, WN_T, 2, 0, WN_GRID_CAP, p);      // (64 couts per workgroup; no M-tile count)
+    return 0;
+}
 
 // called by tnr_conv_forward (conv_tile.hip) for a launch whose weight stream is the transform-domain one (wq_form = 1); 1: not for this kernel
 int tnr_launch_conv3x3_wino(const tnr_conv_desc *d, void *stream) { return launch_wino(d, 0, nullptr, stream); }

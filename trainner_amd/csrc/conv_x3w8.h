@@ -161,11 +161,17 @@ inline bool conv3x3_x3w8_ok(const ConvK &k) {
     return k.bf == 2 && !k.reflect && k.ksplit == 1 && k.Cin == k.KinP && (k.Cin % TNR_CK) == 0;
 }
 
-inline int launch_conv3x3_x3w8(ConvK k, hipStream_t s) {
+// the kernel's own tile grid (the launcher's, and what tnr_conv_launch_class reports)
+inline void conv3x3_x3w8_grid(ConvK &k) {
     using G = X3W8;
     k.tiles_x = tnr_cdiv(k.tw_space, G::TW);
     k.tiles_y = tnr_cdiv(k.th_space, G::TH);
     k.ncb = tnr_cdiv(k.Cout, G::NC);
+}
+
+inline int launch_conv3x3_x3w8(ConvK k, hipStream_t s) {
+    using G = X3W8;
+    conv3x3_x3w8_grid(k);
     const int64_t tiles = (int64_t)k.tiles_x * k.tiles_y * k.ncb * k.N;
     static int cus = 0;
     if (const int rc = tnr_kernel_setup(&cus, "conv3x3_x3w8", {{conv3x3_x3w8_kernel, G::LDS_BYTES}})) return rc;

@@ -76,6 +76,7 @@ _SIGS = {
     "tnr_pack_dense_dims": (c_i, [c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_l)]),
     "tnr_pack_dense_dgrad": (c_i, [c_p, c_i, c_l, c_p]),
     "tnr_conv_forward": (c_i, [C.POINTER(ConvDesc), c_p]),
+    "tnr_conv_launch_class": (c_i, [C.POINTER(ConvDesc), C.POINTER(c_i * 12)]),
     "tnr_conv_workspace_bytes": (c_l, [C.POINTER(ConvDesc)]),
     "tnr_conv_wq_bytes": (c_l, [C.POINTER(ConvDesc)]),
     "tnr_conv_wq_pack": (c_i, [C.POINTER(ConvDesc), c_p, c_l, c_p]),

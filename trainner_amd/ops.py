@@ -545,14 +545,20 @@ def conv_plan(x, wp, y, mode=CONV_3x3, epi=None, shuffle=0, layer=None, wino=Non
     return "tile", why
 
 
-def _conv_launch(x, wp, y, mode, wino, shuffle, epi, layer=None, family=None):
-    """The one tnr_conv_forward path (conv, conv_shuffle2) -> the form launched; None: shuffle cannot be folded and nothing ran.  Descriptor; the
-    library's late answers, each asked where conv_plan's answer hangs on it and fed back into the plan on a decline; the launch; the PROFILE record."""
+_DRY_PTR = 64                   # conv_launch_desc(dry=True): stands for a workspace / weight image of the size the library asked for; never dereferenced
+
+
+def conv_launch_desc(x, wp, y, mode=CONV_3x3, wino=None, shuffle=0, epi=None, layer=None, dry=False):
+    """The descriptor tnr_conv_forward gets for this launch -> (form, ConvDesc); (None, None): shuffle cannot be folded.  Descriptor; the
+    library's late answers, each asked where conv_plan's answer hangs on it and fed back into the plan on a decline.
+    dry: nothing is allocated or packed -- ws / wq hold a placeholder address with the byte count the library asked for -- so that
+    conv_launch_class can be asked about views that have no memory behind them (x, wp, y: anything with the attributes read here)."""
+    epi = epi or {}
     d, said = None, {}
     while True:
         form, why = conv_plan(x, wp, y, mode, epi, shuffle, layer, wino, **said)
         if shuffle and form != "stream":
-            return None
+            return None, None
         if d is None:
             lib, d = hip.load(), ConvDesc()
             _conv_desc(d, x, wp, y, mode, **epi)
@@ -561,25 +567,53 @@ def _conv_launch(x, wp, y, mode, wino, shuffle, epi, layer=None, family=None):
         if why == "splitk":
             need = lib.tnr_conv_workspace_bytes(C.byref(d))
             if need > 0:
-                ws = WS.get("splitk@%x" % hip.stream(), need, x.buf.device)
-                d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 8
+                if dry:
+                    d.ws, d.ws_bytes = _DRY_PTR, need
+                else:
+                    ws = WS.get("splitk@%x" % hip.stream(), need, x.buf.device)
+                    d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 8
                 break
             said["splitk"] = False
         elif form == "wino":
-            img = _wino_image(lib, d, wp, x.buf.device)
-            if img is not None:
-                d.wq, d.wq_bytes, d.wq_form = img.data_ptr(), img.numel() * 4, 1
+            need = lib.tnr_conv_wino_bytes(C.byref(d)) if dry else 0
+            img = None if dry else _wino_image(lib, d, wp, x.buf.device)
+            if img is not None or need > 0:
+                d.wq, d.wq_bytes, d.wq_form = (_DRY_PTR, need, 1) if dry else (img.data_ptr(), img.numel() * 4, 1)
                 break
             assert wino is not True, "this launch cannot run in the Winograd form"
             said["wino_ok"] = False
         elif form == "stream":
-            img = _wq_image(lib, d, wp, x.buf.device, tag="shuffle2" if shuffle else None)
-            if img is not None:
-                d.wq, d.wq_bytes = img.data_ptr(), img.numel() * 4
+            need = lib.tnr_conv_wq_bytes(C.byref(d)) if dry else 0
+            img = None if dry else _wq_image(lib, d, wp, x.buf.device, tag="shuffle2" if shuffle else None)
+            if img is not None or need > 0:
+                d.wq, d.wq_bytes = (_DRY_PTR, need) if dry else (img.data_ptr(), img.numel() * 4)
                 break
             said["stream_ok"] = False
         else:
             break
+    return form, d
+
+
+CONV_KERNELS = ("tile", "x3w8", "d4", "s2_d4", "wino")
+
+
+def conv_launch_class(desc):
+    """tnr_conv_launch_class of a ConvDesc (host only, no launch) -> dict: kernel (one of CONV_KERNELS), tw, th, nt, mt, tiles_x, tiles_y, ncb,
+    tiles, ksplit and cap (the persistent grid's workgroups per CU; 0: one workgroup per tile)."""
+    out = (C.c_int32 * 12)()
+    hip.check(hip.load().tnr_conv_launch_class(C.byref(desc), C.byref(out)), "conv_launch_class")
+    q = dict(zip(("kernel", "tw", "th", "nt", "mt", "tiles_x", "tiles_y", "ncb", "tiles", "ksplit", "cap"), out))
+    q["kernel"] = CONV_KERNELS[q["kernel"]]
+    return q
+
+
+def _conv_launch(x, wp, y, mode, wino, shuffle, epi, layer=None, family=None):
+    """The one tnr_conv_forward path (conv, conv_shuffle2) -> the form launched; None: shuffle cannot be folded and nothing ran.
+    conv_launch_desc's descriptor; the launch; the PROFILE record."""
+    form, d = conv_launch_desc(x, wp, y, mode, wino, shuffle, epi, layer)
+    if d is None:
+        return None
+    lib = hip.load()
     t0 = PROFILE.begin() if PROFILE is not None else None
     hip.check(lib.tnr_conv_forward(C.byref(d), hip.stream()), "conv_forward")
     if PROFILE is not None:
