@@ -200,6 +200,18 @@ typedef struct tnr_dense_pack_item {
     int64_t n_out;
 } tnr_dense_pack_item;
 
+/* ESRGAN+ residual paths (network_G `plus: true`; ResidualDenseBlock_5C.forward, RRDBNet_arch.py:153-158: x2 += conv1x1(x),
+ * x4 += x2) as a weight-space transform: one dense block's real conv3..conv5 and conv1x1 weights, the effective copies the
+ * convolution kernels read instead, the gradient w.r.t. those copies, and the real gradients (csrc/dense_plus.hip).            */
+typedef struct tnr_dense_plus_item {
+    const float *w[3];   /* conv3, conv4, conv5 weights, OIHW */
+    const float *p;      /* conv1x1 weight [gc][nf] */
+    float *eff[3];       /* effective conv3..conv5, same shapes (tnr_dense_plus_fold writes) */
+    const float *g[3];   /* gradient w.r.t. eff of ONE backward (tnr_dense_plus_unfold reads) */
+    float *dw[3];        /* gradients of conv3..conv5 (tnr_dense_plus_unfold adds) */
+    float *dp;           /* gradient of conv1x1 (tnr_dense_plus_unfold adds) */
+} tnr_dense_plus_item;
+
 const char *tnr_last_error(void);
 /* ABI version = TNR_ABI_VERSION of the header the library was built from.  It moves whenever a descriptor struct changes size or
  * layout: a caller built against another header would pass a shorter struct and the library would read fields from adjacent memory.
@@ -224,6 +236,17 @@ int tnr_upconv_fold_table(int32_t out[144]);
 int tnr_upconv_wgrad_unfold(const float *dws, float *dw3, int32_t Cout, int32_t Cin, float alpha, float beta, void *stream);
 int tnr_pack_dense_dims(int32_t nf, int32_t gc, int32_t t, int32_t *KoutP, int32_t *KinP, int64_t *n_out);
 int tnr_pack_dense_dgrad(const tnr_dense_pack_item *items_dev, int32_t n, int64_t max_out, void *stream);
+/* items: DEVICE array of n blocks, all of nf features and gc = 32 growth channels (nf 32 or 64).  With [x | x1 | u2 | x3 | u4] in the
+ * block's buffer (u = the activations before the added paths) a plus block is a plain dense block with, per tap,
+ *   eff3[:, x] = w3[:, x] + w3[:, x2] P,   eff4[:, x] = w4[:, x] + w4[:, x2] P,
+ *   eff5[:, x] = w5[:, x] + (w5[:, x2] + w5[:, x4]) P,   eff5[:, x2] = w5[:, x2] + w5[:, x4],
+ * every other slice copied.  One launch, one workgroup per (block, layer, tap); per element one fp32 FMA chain over ascending k
+ * that starts from the original value.                                                                                        */
+int tnr_dense_plus_fold(const tnr_dense_plus_item *items_dev, int32_t n, int32_t nf, int32_t gc, void *stream);
+/* The adjoint, ADDED into dw / dp:  dw_L += g_L;  dw_L[:, x2] += g_L[:, x] P^T (L = 3, 4, 5);  dw5[:, x4] += g5[:, x2] + g5[:, x] P^T;
+ *   dp += sum over taps of w3[:, x2]^T g3[:, x] + w4[:, x2]^T g4[:, x] + (w5[:, x2] + w5[:, x4])^T g5[:, x].
+ * g is only read.  dp is reduced by one workgroup per block in a fixed order (no atomics): equal inputs give equal bits.         */
+int tnr_dense_plus_unfold(const tnr_dense_plus_item *items_dev, int32_t n, int32_t nf, int32_t gc, void *stream);
 int tnr_conv_forward(const tnr_conv_desc *d, void *stream);
 /* Host-only query (no device, no launch, no memory behind the descriptor's pointers is read): what tnr_conv_forward launches for the
  * descriptor AS IT STANDS -- wq / wq_form / ws / shuffle set or not --, through the code the entry itself decides by.  out[0] the kernel

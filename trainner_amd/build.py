@@ -11,8 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtrainner_hip.so")
-SOURCES = ["conv_tile.hip", "conv_chain.hip", "conv_sweep.hip", "conv_wino.hip", "conv_thin.hip", "wgrad_tile.hip", "wgrad_thin.hip", "pack_api.hip", "elementwise.hip", "norm_loss_optim.hip", "optimizers.hip", "metrics.hip", "feed.hip", "degrade.hip", "dp_api.hip", "gconv.hip", "lpips.hip", "ssim_loss.hip", "image_losses.hip", "pooled_losses.hip", "spl_loss.hip", "freqsep.hip", "diffaug.hip", "batchaug.hip", "gram.hip", "contextual.hip", "spectral_norm.hip"]
+SOURCES = ["conv_tile.hip", "conv_chain.hip", "conv_sweep.hip", "conv_wino.hip", "conv_thin.hip", "wgrad_tile.hip", "wgrad_thin.hip", "pack_api.hip", "elementwise.hip", "norm_loss_optim.hip", "optimizers.hip", "metrics.hip", "feed.hip", "degrade.hip", "dp_api.hip", "gconv.hip", "lpips.hip", "ssim_loss.hip", "image_losses.hip", "pooled_losses.hip", "spl_loss.hip", "freqsep.hip", "diffaug.hip", "batchaug.hip", "gram.hip", "contextual.hip", "spectral_norm.hip", "dense_plus.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
+# per source: dense_plus.hip's error bounds are those of one scalar fp32 FMA chain per element -- no packed fp32 VALU forms
+EXTRA_FLAGS = {"dense_plus.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -55,7 +57,7 @@ def build(force=False, verbose=True):
 
     def compile_one(src):
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
-        cmd = [cc, *FLAGS, "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [cc, *FLAGS, *EXTRA_FLAGS.get(src, ()), "-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed for %s:\n%s" % (src, r.stderr[-4000:]))

@@ -66,6 +66,10 @@ class DensePackItem(C.Structure):
                 ("scale5", c_f), ("n_out", c_l)]
 
 
+class DensePlusItem(C.Structure):
+    _fields_ = [("w", c_p * 3), ("p", c_p), ("eff", c_p * 3), ("g", c_p * 3), ("dw", c_p * 3), ("dp", c_p)]
+
+
 _SIGS = {
     "tnr_last_error": (C.c_char_p, []),
     "tnr_version": (c_i, []),
@@ -75,6 +79,8 @@ _SIGS = {
     "tnr_upconv_wgrad_unfold": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
     "tnr_pack_dense_dims": (c_i, [c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_l)]),
     "tnr_pack_dense_dgrad": (c_i, [c_p, c_i, c_l, c_p]),
+    "tnr_dense_plus_fold": (c_i, [c_p, c_i, c_i, c_i, c_p]),
+    "tnr_dense_plus_unfold": (c_i, [c_p, c_i, c_i, c_i, c_p]),
     "tnr_conv_forward": (c_i, [C.POINTER(ConvDesc), c_p]),
     "tnr_conv_launch_class": (c_i, [C.POINTER(ConvDesc), C.POINTER(c_i * 12)]),
     "tnr_conv_workspace_bytes": (c_l, [C.POINTER(ConvDesc)]),

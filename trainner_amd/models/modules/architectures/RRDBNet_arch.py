@@ -9,6 +9,8 @@ ResidualDenseBlock_5C :98-163), re-designed for CDNA4:
     (:152-160) never happen;
   * bias, LeakyReLU(0.2), `x5*0.2 + x` and the RRDB-level `out*0.2 + x` are epilogues of the
     implicit-GEMM kernel (conv5 of RDB3 carries both residuals);
+  * the ESRGAN+ residual paths (`plus`: x2 += conv1x1(x), x4 += x2, :153-158) live in the WEIGHTS: the buffer keeps the plain
+    activations and conv3..conv5 run on effective weights folded from the real ones and conv1x1 (csrc/dense_plus.hip, ops.DensePlus);
   * the nearest x2 of upconv_block is folded into the following conv's gather;
   * backward is a hand-written schedule.  The data-gradient of a dense block runs as a "gradient
     dense block", the mirror image of the forward: with the gradient buffer laid out
@@ -30,8 +32,10 @@ from . import block as B
 
 
 class ResidualDenseBlock_5C(nn.Module):
-    def __init__(self, nf=64, gc=32, act_type="leakyrelu"):
+    def __init__(self, nf=64, gc=32, act_type="leakyrelu", plus=False):
         super().__init__()
+        if plus:             # ESRGAN+ (:127): declared first, so `conv1x1.weight` leads the block's state_dict as in the reference
+            self.conv1x1 = B.Conv2dHIP(nf, gc, 1, 1, bias=False)
         self.conv1 = B.conv_block(nf, gc, 3, act_type=act_type)
         self.conv2 = B.conv_block(nf + gc, gc, 3, act_type=act_type)
         self.conv3 = B.conv_block(nf + 2 * gc, gc, 3, act_type=act_type)
@@ -40,11 +44,20 @@ class ResidualDenseBlock_5C(nn.Module):
 
 
 class RRDB(nn.Module):
-    def __init__(self, nf, gc=32, act_type="leakyrelu"):
+    def __init__(self, nf, gc=32, act_type="leakyrelu", plus=False):
         super().__init__()
-        self.RDB1 = ResidualDenseBlock_5C(nf, gc, act_type)
-        self.RDB2 = ResidualDenseBlock_5C(nf, gc, act_type)
-        self.RDB3 = ResidualDenseBlock_5C(nf, gc, act_type)
+        self.RDB1 = ResidualDenseBlock_5C(nf, gc, act_type, plus)
+        self.RDB2 = ResidualDenseBlock_5C(nf, gc, act_type, plus)
+        self.RDB3 = ResidualDenseBlock_5C(nf, gc, act_type, plus)
+
+
+class _EffectiveConv:
+    """What ConvOp asks of a layer, for a convolution of an ESRGAN+ dense block whose kernels read an effective weight (ops.DensePlus):
+    `weight` is that tensor and `weight.grad` the shadow gradient its weight-gradient launches accumulate into; the bias is the layer's own."""
+
+    def __init__(self, mod, weight):
+        self.weight, self.bias = weight, mod.bias
+        self.kernel_size, self.stride, self.in_channels, self.out_channels = mod.kernel_size, mod.stride, mod.in_channels, mod.out_channels
 
 
 class RRDBNet(HipNet):
@@ -52,8 +65,10 @@ class RRDBNet(HipNet):
                  mode="CNA", upsample_mode="upconv", convtype="Conv2D", finalact=None, gaussian_noise=False,
                  plus=False):
         super().__init__()
-        if nr != 3 or norm_type is not None or mode != "CNA" or convtype != "Conv2D" or finalact or plus:
+        if nr != 3 or norm_type is not None or mode != "CNA" or convtype != "Conv2D" or finalact:
             raise NotImplementedError("RRDBNet option outside the ESRGAN recipe is not implemented by the HIP engine")
+        if plus and nf not in (32, 64):
+            raise NotImplementedError("RRDBNet plus: the weight-space fold (csrc/dense_plus.hip) is built for nf 32 and 64")
         if upscale not in (2, 4, 8) or upsample_mode not in ("upconv", "pixelshuffle"):
             raise NotImplementedError("upscale %s / upsample mode [%s] is not found" % (upscale, upsample_mode))
         if nf % 32 or in_nc > 4 or out_nc > 4:
@@ -68,9 +83,13 @@ class RRDBNet(HipNet):
         # (what util.set_random_seed pins); noise_sample0: index of this rank's first sample in the global batch.
         self.noise_sigma = 0.1 if gaussian_noise else 0.0
         self.noise_seed, self.noise_sample0, self._noise_calls = None, 0, 0
+        # ESRGAN+ residual paths (x2 += conv1x1(x), x4 += x2; ResidualDenseBlock_5C.forward :153-158).  The dense-block buffers keep the
+        # plain activations [x | x1 | u2 | x3 | u4] and conv3..conv5 run on EFFECTIVE weights that carry the added paths (ops.DensePlus:
+        # one fold launch per weight generation, one unfold launch per RRDB in the backward); no convolution kernel knows of it.
+        self.plus, self._plus = bool(plus), None
 
         fea_conv = B.conv_block(in_nc, nf, 3, act_type=None)
-        trunk = [RRDB(nf, 32, act_type) for _ in range(nb)] + [B.conv_block(nf, nf, 3, act_type=None)]
+        trunk = [RRDB(nf, 32, act_type, self.plus) for _ in range(nb)] + [B.conv_block(nf, nf, 3, act_type=None)]
         ups = []
         for _ in range(self.n_up):
             if upsample_mode == "upconv":
@@ -89,9 +108,18 @@ class RRDBNet(HipNet):
         o = {"fea": ConvOp(m[0], packer, need_dgrad=False)}
         sub = m[1].sub
         o["rdb"], o["rdb_dense"] = [], []
+        rdbs = [r for b in range(self.nb) for r in (sub[b].RDB1, sub[b].RDB2, sub[b].RDB3)]
+        self._plus = None
+        if self.plus and rdbs:
+            self._plus = ops.DensePlus([(r.conv1x1.weight,) + tuple(getattr(r, "conv%d" % k)[0].weight for k in (3, 4, 5)) for r in rdbs],
+                                       self.nf, self.gc, packer.device)
+        # the parameter that leads each RRDB in the flat buffer (what the backward marks as final for the gradient buckets)
+        o["rrdb_first"] = [sub[b].RDB1.conv1x1.weight if self.plus else sub[b].RDB1.conv1[0].weight for b in range(self.nb)]
         for b in range(self.nb):
             for ri, r in enumerate((sub[b].RDB1, sub[b].RDB2, sub[b].RDB3)):
                 convs = [getattr(r, "conv%d" % k)[0] for k in range(1, 6)]
+                if self._plus is not None:
+                    convs[2:] = [_EffectiveConv(c, e) for c, e in zip(convs[2:], self._plus.eff[3 * b + ri])]
                 o["rdb"].append([ConvOp(c, packer, need_dgrad=False) for c in convs])
                 s = 0.2 if ri == 2 else 1.0      # RDB3's output is scaled by the RRDB residual (x0.2)
                 o["rdb_dense"].append(self._dense_packer.add_block([c.weight for c in convs], self.nf, self.gc, 0.2 * s))
@@ -107,6 +135,10 @@ class RRDBNet(HipNet):
         o["hr0"] = ConvOp(m[idx], packer)
         o["hr1"] = ConvOp(m[idx + 2], packer)
         self._ops = o
+
+    def _refresh_derived(self):
+        if self._plus is not None:
+            self._plus.fold()
 
     def engine_forward(self, x, save):
         o, nf, gc = self._ops, self.nf, self.gc
@@ -248,7 +280,7 @@ class RRDBNet(HipNet):
             for k in (3, 2, 1, 0):
                 cin = nf + gc * k
                 gk = View(GP, nf + (3 - k) * gc, gc)
-                big = 4 * gc if cin >= 4 * gc else 2 * gc
+                big = 4 * gc if cin >= 4 * gc else min(2 * gc, cin)      # (nf 32: conv1 reads 32 channels)
                 pieces = [(0, big)] + ([(big, cin - big)] if cin > big else [])
                 for lo, n in pieces:
                     pend.setdefault(n, []).append(convs[k].wgrad_item(View(buf, lo, n), gk, cin_begin=lo))
@@ -275,7 +307,10 @@ class RRDBNet(HipNet):
 
         def done(op):
             if sched is not None:
-                sched.mark_done(op.mod.weight)
+                sched.mark_done(op if isinstance(op, torch.Tensor) else op.mod.weight)
+
+        if W and self._plus is not None:
+            self._plus.begin_backward()
 
         if W:
             o["hr1"].wgrad(h0, View(g4, 0, self.out_nc))
@@ -345,7 +380,9 @@ class RRDBNet(HipNet):
                     ops.gauss_mult(View(G[t], 0, nf), leave, nz[3 * b - 1])
             if W:
                 self._flush_wgrads(pend)
-                done(convs[3 * b][0])                  # everything from this RRDB's first conv onwards is final
+                if self._plus is not None:             # the three blocks' shadow gradients -> conv3..conv5 and conv1x1
+                    self._plus.unfold(3 * b, 3)
+                done(o["rrdb_first"][b])               # everything from this RRDB's first parameter onwards is final
         gfea = P[pc] if P else View(G[pin], 0, nf)
         ops.axpby(gfea, gy0, 1.0, 1.0)                 # ShortcutBlock: both branches reach fea
         if W:

@@ -140,6 +140,8 @@ def mod2normal(state_dict):
             out["%s.%s" % (_NEW_HEAD[name], leaf)] = v
         elif name == "trunk_conv":
             out["model.1.sub.%d.%s" % (nb, leaf)] = v
+        elif name.startswith("RRDB_trunk.") and name.endswith(".conv1x1"):    # ESRGAN+ (`plus`): a bare convolution, no conv_block around it
+            out["model.1.sub.%s.%s" % (name[len("RRDB_trunk."):], leaf)] = v
         elif name.startswith("RRDB_trunk."):
             out["model.1.sub.%s.0.%s" % (name[len("RRDB_trunk."):], leaf)] = v
         else:
@@ -161,6 +163,8 @@ def normal2mod(state_dict):
             out["%s.%s" % (old_head[name], leaf)] = v
         elif name == "model.1.sub.%d" % nb:
             out["trunk_conv.%s" % leaf] = v
+        elif name.startswith("model.1.sub.") and name.endswith(".conv1x1"):
+            out["RRDB_trunk.%s.%s" % (name[len("model.1.sub."):], leaf)] = v
         elif name.startswith("model.1.sub.") and name.endswith(".0"):
             out["RRDB_trunk.%s.%s" % (name[len("model.1.sub."):-2], leaf)] = v
         else:

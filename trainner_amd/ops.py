@@ -209,6 +209,63 @@ class DensePacker:
         self.gen += 1
 
 
+class DensePlus:
+    """The ESRGAN+ dense blocks of one network in weight space (csrc/dense_plus.hip).
+
+    blocks: per dense block the real parameters (p, w3, w4, w5) -- conv1x1 [gc, nf, 1, 1] and conv3..conv5 -- whose `.grad` are the
+    real gradients.  `eff[b]` holds the block's three effective weights, the tensors the packers and the convolution kernels read in
+    place of conv3..conv5; each carries as `.grad` its slice of the shadow gradient buffer, where the weight-gradient launches of ONE
+    backward accumulate (begin_backward() clears it, unfold() takes it into the real gradients)."""
+
+    def __init__(self, blocks, nf, gc, device):
+        self.blocks, self.nf, self.gc, self.device = [tuple(b) for b in blocks], nf, gc, device
+        al = lambda n: round_up(n, 64)
+        total = sum(al(w.numel()) for b in self.blocks for w in b[1:])
+        self.flat = torch.zeros(total, dtype=torch.float32, device=device)
+        self.gflat = torch.zeros(total, dtype=torch.float32, device=device)
+        self.eff, off = [], 0
+        for b in self.blocks:
+            row = []
+            for w in b[1:]:
+                e = self.flat[off:off + w.numel()].view(w.shape)
+                e.grad = self.gflat[off:off + w.numel()].view(w.shape)
+                row.append(e)
+                off += al(w.numel())
+            self.eff.append(row)
+        self.table, self._ptrs = None, None
+
+    def _live_ptrs(self):
+        return [q for b in self.blocks for t in b for q in (t.data_ptr(), hip.ptr(t.grad))]
+
+    def _ensure(self):
+        if self._ptrs != self._live_ptrs():
+            items = (hip.DensePlusItem * len(self.blocks))()
+            for i, (b, e) in enumerate(zip(self.blocks, self.eff)):
+                it = hip.DensePlusItem()
+                it.p, it.dp = b[0].data_ptr(), hip.ptr(b[0].grad)
+                for k in range(3):
+                    it.w[k], it.eff[k], it.g[k], it.dw[k] = b[1 + k].data_ptr(), e[k].data_ptr(), e[k].grad.data_ptr(), hip.ptr(b[1 + k].grad)
+                items[i] = it
+            self.table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.device)
+            self._ptrs = self._live_ptrs()
+        return self.table
+
+    def fold(self):
+        """Every block's effective conv3..conv5 from the current parameters: one launch."""
+        t = self._ensure()
+        hip.check(hip.load().tnr_dense_plus_fold(t.data_ptr(), len(self.blocks), self.nf, self.gc, hip.stream()), "dense_plus_fold")
+
+    def begin_backward(self):
+        fill(self.gflat, 0.0)
+
+    def unfold(self, first, n):
+        """Blocks [first, first + n): the shadow gradient into the real gradients of conv3..conv5 and conv1x1 (added): one launch."""
+        t = self._ensure()
+        assert 0 <= first and first + n <= len(self.blocks) and all(q is not None for q in self._ptrs)
+        at = t.data_ptr() + first * C.sizeof(hip.DensePlusItem)
+        hip.check(hip.load().tnr_dense_plus_unfold(at, n, self.nf, self.gc, hip.stream()), "dense_plus_unfold")
+
+
 # ----------------------------------------------------------------------------------------------
 # spectral normalisation (csrc/spectral_norm.hip)
 # ----------------------------------------------------------------------------------------------
