@@ -66,7 +66,11 @@ enum {
      * W_S[ci][co][ky][kx] = sum of W[co][ci][ty][tx] over ty in T(ky), tx in T(kx), T = {2}, {1,2}, {0,1}, {0} (tnr_upconv_fold_table;
      * fp32, added inside a row over ascending tx first, then the rows over ascending ty).  Both are made straight from the 3x3 tensor: */
     TNR_PACK_UP2_DGRAD_S2 = 8, /* TNR_PACK_DGRAD_S2's layout of S, [4 parities][4][KoutP=co][KinP=ci]: the layer's FORWARD as TNR_DGRAD_4x4_S2 */
-    TNR_PACK_UP2_FWD_S2D = 9   /* TNR_PACK_FWD_S2D's layout of S, [4][KoutP=ci][4*KinP=co]: its DATA-GRADIENT (the x2 sum included) as TNR_CONV_4x4_S2 */
+    TNR_PACK_UP2_FWD_S2D = 9,  /* TNR_PACK_FWD_S2D's layout of S, [4][KoutP=ci][4*KinP=co]: its DATA-GRADIENT (the x2 sum included) as TNR_CONV_4x4_S2 */
+    /* The 3x3 layer behind a pixel unshuffle of s = 2 | 4 (Cin = 3 s^2 = 12 | 48) as its (3s) x (3s) stride-s window over the NHWC4 image,
+     * for tnr_conv_unshuffle_fwd: [K / 8][Cout][8], K index ((wy * 3s + wx) * 4 + c) <- W[co][c s^2 + (wy % s) s + wx % s][wy / s][wx / s],
+     * zeros for the pad channel c = 3.  KoutP = Cout (a multiple of 32), KinP = K = 144 | 576.                                      */
+    TNR_PACK_UNSHUFFLE_FWD = 10
 };
 
 #define TNR_MMA_F32 0
@@ -357,6 +361,22 @@ int64_t tnr_wgrad_thin7_workspace_bytes(int32_t N, int32_t Hbig_grid, int32_t Cb
 int tnr_wgrad_thin7(tnr_view big, int32_t N, int32_t H, int32_t W, int32_t rpad, tnr_view small, int32_t Hs, int32_t Ws, int32_t off,
                     int32_t Cbig, int32_t Csmall, int32_t flip, float *dw, float *db, float alpha, float beta, float *ws, int64_t ws_bytes,
                     void *stream);
+/* The generator's first layer behind a pixel unshuffle (use_unshuffle / unshuffle_scale, options/defaults.py:19-33; block.SpaceToDepth
+ * 'pt' = F.pixel_unshuffle in front of RRDBNet's fea conv, sr_model.py:144-153) as ONE convolution over the image itself -- window
+ * (3s) x (3s), stride s, padding s -- so that the unshuffled tensor is never stored:
+ *   y[n, Y, X, co] = bias[co] + sum W[co][c s^2 + i s + j][dy][dx] * x[n, (Y + dy - 1) s + i, (X + dx - 1) s + j, c]     (0 outside the image)
+ * x: the NHWC4 image [N, H, W, 4] (channel 3 is never multiplied by a non-zero weight), H and W multiples of s in {2, 4};
+ * y: [N, H / s, W / s, nf] view, nf in {32, 64}; wp: TNR_PACK_UNSHUFFLE_FWD; mma: TNR_MMA_* as in tnr_conv_desc.  One workgroup stages
+ * the image halo of an 8 x 16 output tile in LDS once and folds the window into K on the matrix core (csrc/conv_unshuffle.hip).
+ * tnr_wgrad_unshuffle: dw[co][c s^2 + i s + j][dy][dx] = beta dw + alpha sum_{n, Y, X} g[n, Y, X, co] x[n, (Y + dy - 1) s + i, (X + dx - 1) s + j, c]
+ * (OIHW [nf][3 s^2][3][3]) and db = beta db + alpha sum g (db may be NULL): fp32 matrix-core products over persistent workgroups,
+ * partial slabs in ws (tnr_wgrad_unshuffle_workspace_bytes) added in a fixed order by a second launch.  Deterministic.
+ * There is no data gradient: the input is the image.                                                                               */
+int tnr_conv_unshuffle_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, const float *wp, tnr_view y, int32_t nf, int32_t s,
+                           const float *bias, int32_t mma, void *stream);
+int64_t tnr_wgrad_unshuffle_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t nf, int32_t s);
+int tnr_wgrad_unshuffle(tnr_view g, tnr_view x, int32_t N, int32_t H, int32_t W, int32_t nf, int32_t s, float *dw, float *db,
+                        float alpha, float beta, float *ws, int64_t ws_bytes, void *stream);
 int tnr_conv_wgrad(const tnr_wgrad_desc *d, void *stream);
 /* n <= TNR_WGRAD_GROUP_MAX layers in ONE launch (+ one reduce launch).  The layers must share mode and
  * N/H/W/Ho/Wo and fall into the same workgroup tile class (same Cout <= 32 | > 32 and the same number of

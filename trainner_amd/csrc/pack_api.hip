@@ -74,6 +74,12 @@ extern "C" int tnr_pack_dims(int32_t Cout, int32_t Cin, int32_t kh, int32_t kw, 
             ko = tnr_round_up(Cin, 32); ki = tnr_round_up(4 * kh * kw, TNR_CK);
             n = (int64_t)ko * ki;
             break;
+        case TNR_PACK_UNSHUFFLE_FWD:
+            TNR_REQUIRE(kh == 3 && kw == 3 && (Cin == 12 || Cin == 48) && Cout % 32 == 0,
+                        "pack unshuffle: a 3x3 kernel over 3 s^2 = 12 or 48 input channels, Cout %% 32 == 0");
+            ko = Cout; ki = 12 * Cin;      // K = (3s)^2 * 4 = 144 | 576
+            n = (int64_t)ko * ki;
+            break;
         case TNR_PACK_UP2_DGRAD_S2:   // the folded S has Cout_S = Cin, Cin_S = Cout: its data-gradient produces the layer's Cout channels
             TNR_REQUIRE(kh == 3 && kw == 3, "pack up2 dgrad s2: kernel must be 3x3");
             ko = tnr_round_up(Cout, 32); ki = tnr_round_up(Cin, TNR_CK);
@@ -141,6 +147,12 @@ __global__ void pack_weights_kernel(const tnr_pack_item *items) {
             const int ci = (int)(e / ki);
             const int t = v_ >> 2, co = v_ & 3;
             if (ci < Cin && t < kh * kw && co < Cout) v = it.w[(((size_t)co * Cin + ci) * kh + (kh - 1 - t / kw)) * kw + (kw - 1 - t % kw)];
+        } else if (it.kind == TNR_PACK_UNSHUFFLE_FWD) {  // [K / 8][co][8], K index = ((wy * 3s + wx) * 4 + c): window pixel, image channel
+            const int k = (int)(e / (8 * ko)) * 8 + (int)(e & 7);
+            const int co = (int)((e >> 3) % ko);
+            const int s = Cin == 12 ? 2 : 4, c = k & 3, wy = (k >> 2) / (3 * s), wx = (k >> 2) - wy * 3 * s;
+            // window position (dy s + i, dx s + j) of channel c is pixel_unshuffle channel c s^2 + i s + j of tap (dy, dx)
+            if (c < 3) v = it.w[(((size_t)co * Cin + c * s * s + (wy % s) * s + wx % s) * 3 + wy / s) * 3 + wx / s];
         } else if (it.kind == TNR_PACK_UP2_DGRAD_S2) {   // TNR_PACK_DGRAD_S2's layout of the folded S: [par][t][co][ci], W_S[ci][co] = fold(w[co][ci])
             const int ci = (int)(e % ki);              // reduction channel = the 3x3 layer's input
             int64_t q = e / ki;

@@ -136,6 +136,24 @@ class ConvOp:
         ops.wgrad_group([self.wgrad_item(x, g, alpha, cin_begin, with_bias)], mode=self.mode_f)
 
 
+class UnshuffleConvOp:
+    """A generator's first 3x3 layer behind a pixel unshuffle of s (in_channels = 3 s^2): forward and weight gradient read the NHWC4
+    image itself through the layer's (3s) x (3s) stride-s window (csrc/conv_unshuffle.hip).  The input is the image: no data gradient."""
+
+    def __init__(self, mod, packer, s):
+        if mod.kernel_size != 3 or mod.stride != 1 or mod.in_channels != 3 * s * s or mod.out_channels not in (32, 64):
+            raise NotImplementedError("unshuffle layer: a 3x3 stride-1 conv of %d -> 32 | 64 channels" % (3 * s * s))
+        self.mod, self.packer, self.s = mod, packer, s
+        self.i_f = packer.add(mod.weight, ops.PACK_UNSHUFFLE_FWD)
+
+    def fwd(self, img, y):
+        ops.conv_unshuffle(img, self.packer.get(self.i_f), y, self.s, bias=self.mod.bias)
+
+    def wgrad(self, img, g, alpha=1.0):
+        m = self.mod
+        ops.wgrad_unshuffle(g, img, m.weight.grad, None if m.bias is None else m.bias.grad, self.s, alpha=alpha, beta=1.0)
+
+
 class SpectralNormState:
     """The spectrally normalised convolutions of one network (block.SpectralNormConv2dHIP) and their weight generations.
 

@@ -22,6 +22,7 @@ CONV_3x3, CONV_3x3_UP2, CONV_4x4_S2, DGRAD_4x4_S2, CONV_1x1, CONV_3x3_C4, CONV_7
 PACK_FWD, PACK_DGRAD_3x3, PACK_FWD_S2D, PACK_DGRAD_S2, PACK_COL_FWD, PACK_COL_DGRAD3 = 0, 1, 2, 3, 4, 5
 PACK_C4_FWD, PACK_C4_DGRAD3 = 6, 7
 PACK_UP2_DGRAD_S2, PACK_UP2_FWD_S2D = 8, 9      # a nearest-x2 3x3 layer folded into its virtual 4x4 stride-2 convolution
+PACK_UNSHUFFLE_FWD = 10                         # the fea layer behind a pixel unshuffle: its (3s) x (3s) stride-s window over the image
 PACK_DENSE_DGRAD = 16      # host-side tag of tnr_pack_dense_dgrad slabs (consumed like PACK_FWD by conv_tile)
 
 
@@ -108,6 +109,9 @@ _SIGS = {
     "tnr_wgrad_thin7": (c_i, [CView, c_i, c_i, c_i, c_i, CView, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_l, c_p]),
     "tnr_wgrad_thin_workspace_bytes": (c_l, [c_i, c_i, c_i]),
     "tnr_wgrad_thin": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_l, c_p]),
+    "tnr_conv_unshuffle_fwd": (c_i, [CView, c_i, c_i, c_i, c_p, CView, c_i, c_i, c_p, c_i, c_p]),
+    "tnr_wgrad_unshuffle_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i]),
+    "tnr_wgrad_unshuffle": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_l, c_p]),
     "tnr_conv_wgrad": (c_i, [C.POINTER(WgradDesc), c_p]),
     "tnr_conv_wgrad_group": (c_i, [C.POINTER(WgradDesc), c_i, c_p]),
     "tnr_wgrad_tile_class": (c_i, [C.POINTER(WgradDesc), c_i, C.POINTER(c_i * 12)]),

@@ -453,7 +453,14 @@ class BaseModel:
         self._reject(self.opt.get("use_cem"), "CEM (use_cem)")
 
     def setup_unshuffle(self):
-        self._reject(self.opt.get("use_unshuffle"), "pixel unshuffle wrapper")
+        unshuffle_scale = self.opt.get("unshuffle_scale")
+        if self.opt.get("use_unshuffle") and unshuffle_scale:
+            from .modules.architectures.block import SpaceToDepth
+            if getattr(getattr(self, "netG", None), "unshuffle", None) != unshuffle_scale:
+                raise NotImplementedError("use_unshuffle: the HIP engine runs the pixel unshuffle inside RRDBNet's first layer, for an RGB image "
+                                          "and a scale of 2 or 4 (network_G in_nc 12 / 48); a grayscale image or another generator is not implemented")
+            self.unshuffle = SpaceToDepth(unshuffle_scale)
+            logger.info("Pixel Unshuffle wrapper enabled. " f"Scale: {unshuffle_scale}")
 
     def setup_gradclip(self, clip_nets):
         train_opt = self.opt["train"]

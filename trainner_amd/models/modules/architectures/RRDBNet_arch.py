@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from .... import ops
-from ....engine import ConvOp, HipNet
+from ....engine import ConvOp, HipNet, UnshuffleConvOp
 from ....ops import View, new_act
 from . import block as B
 
@@ -71,8 +71,17 @@ class RRDBNet(HipNet):
             raise NotImplementedError("RRDBNet plus: the weight-space fold (csrc/dense_plus.hip) is built for nf 32 and 64")
         if upscale not in (2, 4, 8) or upsample_mode not in ("upconv", "pixelshuffle"):
             raise NotImplementedError("upscale %s / upsample mode [%s] is not found" % (upscale, upsample_mode))
-        if nf % 32 or in_nc > 4 or out_nc > 4:
-            raise NotImplementedError("HIP RRDBNet needs nf %% 32 == 0 and <= 4 image channels")
+        # in_nc 12 / 48: the RGB image behind a pixel unshuffle of 2 / 4 (use_unshuffle: the x2 and x1 models keep the x4 network).  The
+        # first layer keeps the reference's [nf, in_nc, 3, 3] weight and reads the image itself (engine.UnshuffleConvOp).
+        self.unshuffle = {12: 2, 48: 4}.get(in_nc, 0)
+        if in_nc == 16:      # (in_nc 4 = grayscale behind an unshuffle of 2 cannot be told from a 4-channel image here: BaseModel.setup_unshuffle refuses it)
+            raise NotImplementedError("RRDBNet in_nc 16 (a grayscale image behind a pixel unshuffle of 4) is not implemented by the HIP engine: "
+                                      "the unshuffle layer reads a 3-channel image")
+        if self.unshuffle and nf not in (32, 64):
+            raise NotImplementedError("RRDBNet in_nc %d (pixel unshuffle): the unshuffle layer is built for nf 32 and 64" % in_nc)
+        if nf % 32 or (in_nc > 4 and not self.unshuffle) or out_nc > 4:
+            raise NotImplementedError("HIP RRDBNet needs nf %% 32 == 0 and in_nc <= 3 (or 12 / 48: RGB behind a pixel unshuffle of 2 / 4), "
+                                      "got in_nc %d" % in_nc)
         self.in_nc, self.out_nc, self.nf, self.nb, self.gc = in_nc, out_nc, nf, nb, 32  # reference ignores gc (:24)
         self.upsample_mode, self.n_up = upsample_mode, int(math.log(upscale, 2))
         self.act, self.slope = B.act_code(act_type)
@@ -105,7 +114,7 @@ class RRDBNet(HipNet):
     # ------------------------------------------------------------------------------ engine
     def _build_ops(self, packer):
         m = self.model
-        o = {"fea": ConvOp(m[0], packer, need_dgrad=False)}
+        o = {"fea": UnshuffleConvOp(m[0], packer, self.unshuffle) if self.unshuffle else ConvOp(m[0], packer, need_dgrad=False)}
         sub = m[1].sub
         o["rdb"], o["rdb_dense"] = [], []
         rdbs = [r for b in range(self.nb) for r in (sub[b].RDB1, sub[b].RDB2, sub[b].RDB3)]
@@ -148,6 +157,8 @@ class RRDBNet(HipNet):
         cb = nf + 4 * gc
         lr = new_act(N, h, w, 4, dev)
         ops.nchw_to_nhwc(x, View(lr), Cpad=4)
+        if self.unshuffle:                         # x is the image (forward() saw to that); the trunk runs at 1 / s of it
+            h, w = h // self.unshuffle, w // self.unshuffle
         nrdb = 3 * self.nb
         nz = self._draw_noise(nrdb, h * w)         # per dense block: ops.Noise, or None (eval mode / sigma 0)
         nbuf = nrdb if save else min(nrdb, 4)
@@ -386,7 +397,7 @@ class RRDBNet(HipNet):
         gfea = P[pc] if P else View(G[pin], 0, nf)
         ops.axpby(gfea, gy0, 1.0, 1.0)                 # ShortcutBlock: both branches reach fea
         if W:
-            o["fea"].wgrad(View(sv["lr"], 0, self.in_nc), gfea)
+            o["fea"].wgrad(View(sv["lr"]) if self.unshuffle else View(sv["lr"], 0, self.in_nc), gfea)
         gx = None
         if need_input_grad:
             raise NotImplementedError("gradient w.r.t. the LR input is not on the SR training path")
@@ -395,4 +406,13 @@ class RRDBNet(HipNet):
     def forward(self, x, outm=None):
         if outm:
             raise NotImplementedError("finalcap/outm [%s] is not implemented by the HIP engine" % outm)
+        if isinstance(x, B.Unshuffled):            # block.SpaceToDepth's handle: the image and the block size
+            if x.bs != self.unshuffle:
+                raise ValueError("RRDBNet with in_nc %d got an image behind a pixel unshuffle of %d" % (self.in_nc, x.bs))
+            x = x.image
+            if x.shape[1] != 3:
+                raise ValueError("RRDBNet behind a pixel unshuffle reads a 3-channel image, got %d channels" % x.shape[1])
+        elif self.unshuffle:
+            raise ValueError("RRDBNet with in_nc %d reads the image through its pixel unshuffle layer: pass block.SpaceToDepth(%d)(image), not "
+                             "a plain tensor of %d channels (re-forming the image would be an eager detour)" % (self.in_nc, self.unshuffle, x.shape[1]))
         return super().forward(x)

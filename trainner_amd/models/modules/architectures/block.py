@@ -111,6 +111,27 @@ class Marker(nn.Module):
         return self.what
 
 
+class Unshuffled:
+    """What SpaceToDepth hands to the network: the image itself and the block size.  The unshuffled tensor is never formed --
+    RRDBNet's first layer reads the image through the (3 bs) x (3 bs) stride-bs window it amounts to (csrc/conv_unshuffle.hip)."""
+    __slots__ = ("image", "bs")
+
+    def __init__(self, image, bs):
+        self.image, self.bs = image, bs
+
+
+class SpaceToDepth:
+    """block.SpaceToDepth (block.py:493-545) in its default 'pt' form, F.pixel_unshuffle's channel order, as a light handle."""
+
+    def __init__(self, block_size=2):
+        self.bs = block_size
+
+    def __call__(self, x):
+        h, w = x.shape[2], x.shape[3]
+        assert h % self.bs == 0 and w % self.bs == 0, "{}".format((h, w, self.bs))
+        return Unshuffled(x, self.bs)
+
+
 class LinearHIP(nn.Module):
     """nn.Linear's tensors (name contains 'Linear' for init_weights)."""
 

@@ -72,7 +72,8 @@ class SRModel(BaseModel):
             return            # (`use_amp` steps run the bf16-operand forms: no choice to make)
         ds = self.opt["datasets"]["train"]
         per = max(1, int(ds["batch_size"]) // max(1, self.dp.world_size))
-        lr_size = max(8, int(ds.get("crop_size") or 128) // int(self.opt.get("scale") or 4))
+        # (behind a pixel unshuffle the trunk runs at crop_size / scale / unshuffle_scale)
+        lr_size = max(8, int(ds.get("crop_size") or 128) // int(self.opt.get("scale") or 4) // (self.unshuffle.bs if self.unshuffle else 1))
         self.netG.calibrate_dense_block_form(per, lr_size, lr_size, self.dp)
 
     def feed_data(self, data, need_HR=True):
@@ -90,7 +91,10 @@ class SRModel(BaseModel):
 
     def forward(self, data=None, CEM_net=None):
         if isinstance(data, torch.Tensor):
-            return self.netG(data)
+            return self.netG(self.unshuffle(data)) if self.unshuffle is not None else self.netG(data)
+        if self.unshuffle is not None:          # sr_model.py:144-153: the x2 / x1 models hand the x4 net the unshuffled image
+            self.fake_H = self.netG(self.unshuffle(self.var_L))
+            return
         self.fake_H = self.netG(self.var_L, outm=self.outm) if self.outm else self.netG(self.var_L)
 
     def backward_G(self):

@@ -12,7 +12,7 @@ import torch
 from . import hip
 from .hip import (ACT_LRELU, ACT_NONE, ACT_RELU, CONV_1x1, CONV_3x3, CONV_3x3_C4, CONV_3x3_UP2, CONV_4x4_S2, CONV_7x7_C4, DGRAD_4x4_S2,  # noqa: F401
                   PACK_C4_DGRAD3, PACK_C4_FWD, PACK_COL_DGRAD3, PACK_COL_FWD, PACK_DENSE_DGRAD, PACK_DGRAD_3x3, PACK_DGRAD_S2, PACK_FWD, PACK_FWD_S2D, PACK_UP2_DGRAD_S2,
-                  PACK_UP2_FWD_S2D, CView,
+                  PACK_UNSHUFFLE_FWD, PACK_UP2_FWD_S2D, CView,
                   ConvDesc,
                   DensePackItem, PackItem, WgradDesc)
 
@@ -1263,6 +1263,31 @@ def wgrad_thin(big, small4, dw, db, flip, alpha=1.0, beta=1.0):
                                  alpha, beta, ws.data_ptr(), ws.numel() * 8, hip.stream()), "wgrad_thin")
     if PROFILE is not None:
         PROFILE.end("wgrad_thin", 2.0 * big.pixels * 9 * big.C * cs, t0, (big.C, cs, big.H, int(flip)))
+
+
+def conv_unshuffle(x_img, wp, y, s, bias=None):
+    """y = conv3x3(pixel_unshuffle(image, s)) + bias in one launch over the NHWC4 image itself (tnr_conv_unshuffle_fwd): x_img the
+    [N, H, W, 4] image view, wp the layer's PACK_UNSHUFFLE_FWD weights, y an [N, H / s, W / s, nf] view.  Arithmetic: ops.MMA."""
+    if wp.kind != PACK_UNSHUFFLE_FWD or wp.KoutP != y.C or wp.KinP != 36 * s * s:
+        raise hip.HipEngineError("conv_unshuffle: weights are not the PACK_UNSHUFFLE_FWD packing of a [%d, %d, 3, 3] layer" % (y.C, 3 * s * s))
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(hip.load().tnr_conv_unshuffle_fwd(x_img.c(), x_img.N, x_img.H, x_img.W, wp.t.data_ptr(), y.c(), y.C, s, hip.ptr(bias), MMA,
+                                                hip.stream()), "conv_unshuffle_fwd")
+    if PROFILE is not None:
+        PROFILE.end("conv_unshuffle", 2.0 * y.pixels * 27 * s * s * y.C, t0, (3 * s * s, y.C, y.H, s))
+
+
+def wgrad_unshuffle(g, x_img, dw, db, s, alpha=1.0, beta=1.0):
+    """dw ([nf, 3 s^2, 3, 3], OIHW) = beta dw + alpha * the weight gradient of that layer from g = the gradient of its output and the
+    NHWC4 image; db likewise (may be None).  Two launches, deterministic (tnr_wgrad_unshuffle)."""
+    lib = hip.load()
+    need = lib.tnr_wgrad_unshuffle_workspace_bytes(x_img.N, x_img.H, x_img.W, g.C, s)
+    ws = WS.get("wgrad_unshuffle@%x" % hip.stream(), need, g.buf.device)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(lib.tnr_wgrad_unshuffle(g.c(), x_img.c(), x_img.N, x_img.H, x_img.W, g.C, s, dw.data_ptr(), hip.ptr(db), alpha, beta,
+                                      ws.data_ptr(), ws.numel() * 8, hip.stream()), "wgrad_unshuffle")
+    if PROFILE is not None:
+        PROFILE.end("wgrad_unshuffle", 2.0 * g.pixels * 27 * s * s * g.C, t0, (3 * s * s, g.C, g.H, s))
 
 
 # ----------------------------------------------------------------------------------------------

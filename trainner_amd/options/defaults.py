@@ -24,6 +24,16 @@ def _kind_and_dict(net, which):
 def get_network_G_config(network_G, scale, crop_size):
     kind, src = _kind_and_dict(network_G, "which_model_G")
     full = {"strict": src.pop("strict", False)}
+    if src.get("unshuffle"):      # pixel unshuffle in front of the net (defaults.py:19-33): the net sees in_nc * s^2 channels
+        if "unshuffle_scale" in src:
+            unshuffle_scale = src["unshuffle_scale"]
+        else:
+            net_scale = src.get("scale")
+            unshuffle_scale = net_scale // scale if (net_scale and net_scale != scale) else None
+        full["unshuffle_scale"] = unshuffle_scale
+        in_nc = src.get("in_nc", 3)
+        if unshuffle_scale and in_nc == 3 or in_nc == 1:      # (the reference's precedence)
+            src["in_nc"] = in_nc * unshuffle_scale ** 2
     if kind in _RRDB_KINDS:
         nf, nb = _RRDB_KINDS[kind]
         full["type"] = "rrdb_net"
@@ -133,7 +143,14 @@ def get_network_D_config(network_D, scale, crop_size, model_G):
 def get_network_defaults(opt, is_train):
     scale = opt.get("scale", 1)
     crop_size = int(opt["datasets"]["train"]["crop_size"]) if is_train else opt.get("img_size")
-    network_G = get_network_G_config(opt.pop("network_G", None), scale, crop_size)
+    network_G = opt.pop("network_G", None)
+    if opt.get("use_unshuffle") and "unshuffle" not in network_G:      # defaults.py:409-422: the top-level switch reaches network_G
+        network_G["unshuffle"] = True
+        if opt.get("unshuffle_scale") and "unshuffle_scale" not in network_G:
+            network_G["unshuffle_scale"] = opt.get("unshuffle_scale")
+    network_G = get_network_G_config(network_G, scale, crop_size)
+    if "unshuffle_scale" in network_G:
+        opt["unshuffle_scale"] = network_G.pop("unshuffle_scale")      # a global key, as in the reference
     opt["network_G"] = network_G
     if opt.get("network_D", None):
         opt["network_D"] = get_network_D_config(opt.pop("network_D"), scale, crop_size, network_G["type"])
