@@ -70,7 +70,15 @@ enum {
     /* The 3x3 layer behind a pixel unshuffle of s = 2 | 4 (Cin = 3 s^2 = 12 | 48) as its (3s) x (3s) stride-s window over the NHWC4 image,
      * for tnr_conv_unshuffle_fwd: [K / 8][Cout][8], K index ((wy * 3s + wx) * 4 + c) <- W[co][c s^2 + (wy % s) s + wx % s][wy / s][wx / s],
      * zeros for the pad channel c = 3.  KoutP = Cout (a multiple of 32), KinP = K = 144 | 576.                                      */
-    TNR_PACK_UNSHUFFLE_FWD = 10
+    TNR_PACK_UNSHUFFLE_FWD = 10,
+    /* A 3x3 layer behind nearest x3 as the transposed 5x5 s3 p1 convolution it is (csrc/conv_up3.hip): the 25 folded taps
+     * K[ky][kx] = sum of W[co][ci][ty][tx] over ty in T(ky), tx in T(kx), T = {2}, {1,2}, {0,1,2}, {0,1}, {0} (tnr_upconv3_fold_table; fp32,
+     * added inside a row over ascending tx first, then the rows over ascending ty) as the A fragments of the matrix core, in the order the
+     * kernel consumes them.  One image holds the fp32 fragments and behind them the exact bf16 hi / mid / lo planes of the folded taps
+     * (TNR_MMA_BF16 reads the hi plane: the bf16 rounding of the FOLDED tap): n_out = 25 * KoutP * KinP * 5 / 2 floats.
+     * _FWD: KoutP = Cout rows, KinP = Cin reduced, taps by output phase; _DGRAD: KoutP = Cin rows, KinP = Cout reduced, in chunks of 16.   */
+    TNR_PACK_UP3_FWD = 11,
+    TNR_PACK_UP3_DGRAD = 12
 };
 
 #define TNR_MMA_F32 0
@@ -377,6 +385,26 @@ int tnr_conv_unshuffle_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, const fl
 int64_t tnr_wgrad_unshuffle_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t nf, int32_t s);
 int tnr_wgrad_unshuffle(tnr_view g, tnr_view x, int32_t N, int32_t H, int32_t W, int32_t nf, int32_t s, float *dw, float *db,
                         float alpha, float beta, float *ws, int64_t ws_bytes, void *stream);
+/* RRDBNet's x3 up-conv layer (upscale 3: nn.Upsample(scale_factor=3, nearest) + Conv2d(nf, nf, 3, 1, 1) + LeakyReLU, RRDBNet_arch.py:35-36,
+ * block.py:326-371) in its only form here: the transposed 5x5 stride-3 padding-1 convolution of the LOW-resolution tensor over the 25
+ * folded taps (TNR_PACK_UP3_*).  LR pixel i reaches HR outputs 3i - 1 + k, k = 0..4; by output phase (o mod 3) an output reads the LR
+ * neighbours {i-1, i}, {i}, {i, i+1} per axis: 25 products per LR pixel and channel pair instead of 81.  The up-sampled tensor never exists.
+ * nf = channels in and out, 32 or 64; x, gx: [N, H, W, nf] views; y, g: [N, 3H, 3W, nf] views; mma: TNR_MMA_*.
+ *   tnr_upconv3_fwd  : y = act(conv + bias); a workgroup stages an 8 x 16 LR tile + halo (zeros outside) once and runs the nine phases.
+ *   tnr_upconv3_dgrad: gx[i, j] = sum_k K[k]^T g[3i - 1 + ky, 3j - 1 + kx], times LeakyReLU'(mask; m_slope) when mask.ptr != NULL
+ *                      (mask: the [N, H, W, nf] output of the activation that produced the layer's input).
+ *   tnr_upconv3_wgrad: dw[co][ci][3][3] = beta dw + alpha unfold(dK), dK[k][ci][co] = sum over LR pixels of x (x) g of the tap's phase: fp32
+ *                      matrix-core products, partial slabs in ws (tnr_upconv3_wgrad_workspace_bytes) added in a fixed order and unfolded
+ *                      (3x3 tap t <- folded taps 2 - t .. 4 - t per axis) by a second launch.  Deterministic.  db: tnr_bias_grad.
+ * tnr_upconv3_fold_table (host only): out[(ky*5 + kx)*9 + ty*3 + tx] = 1 where folded tap (ky, kx) sums 3x3 tap (ty, tx), else 0.      */
+int tnr_upconv3_fold_table(int32_t out[225]);
+int tnr_upconv3_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, const float *wp, tnr_view y, int32_t nf, const float *bias, int32_t act,
+                    float slope, int32_t mma, void *stream);
+int tnr_upconv3_dgrad(tnr_view g, int32_t N, int32_t H, int32_t W, const float *wp, tnr_view gx, int32_t nf, tnr_view mask, float m_slope,
+                      int32_t mma, void *stream);
+int64_t tnr_upconv3_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t nf);
+int tnr_upconv3_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H, int32_t W, int32_t nf, float *dw, float alpha, float beta, float *ws,
+                      int64_t ws_bytes, void *stream);
 int tnr_conv_wgrad(const tnr_wgrad_desc *d, void *stream);
 /* n <= TNR_WGRAD_GROUP_MAX layers in ONE launch (+ one reduce launch).  The layers must share mode and
  * N/H/W/Ho/Wo and fall into the same workgroup tile class (same Cout <= 32 | > 32 and the same number of

@@ -79,6 +79,30 @@ __host__ __device__ inline float tnr_upfold_grad(const float *dF16, int ty, int 
     return (dF16[ky * 4 + kx] + dF16[ky * 4 + kx + 1]) + (dF16[(ky + 1) * 4 + kx] + dF16[(ky + 1) * 4 + kx + 1]);
 }
 
+// Nearest x3 in front of a 3x3 s1 p1 convolution is the transposed 5x5 s3 p1 convolution of the low-resolution tensor: LR
+// pixel i reaches outputs 3i - 1 + k, and folded tap k = 0..4 sums the 3x3 taps tnr_up3fold_lo(k) .. tnr_up3fold_hi(k) per axis:
+// {2}, {1,2}, {0,1,2}, {0,1}, {0}.  Same fp32 order as tnr_upfold_tap: inside a row over ascending kx first, then the rows over ascending ky.
+__host__ __device__ inline int tnr_up3fold_lo(int k) { return k >= 2 ? 0 : 2 - k; }
+__host__ __device__ inline int tnr_up3fold_hi(int k) { return k <= 2 ? 2 : 4 - k; }
+__host__ __device__ inline float tnr_up3fold_tap(const float *w9, int ky, int kx) {
+    const int ylo = tnr_up3fold_lo(ky), yhi = tnr_up3fold_hi(ky), xlo = tnr_up3fold_lo(kx), xhi = tnr_up3fold_hi(kx);
+    float sum = 0.f;
+    for (int ty = ylo; ty <= yhi; ++ty) {
+        float row = w9[ty * 3 + xlo];
+        for (int tx = xlo + 1; tx <= xhi; ++tx) row = row + w9[ty * 3 + tx];
+        sum = ty == ylo ? row : sum + row;
+    }
+    return sum;
+}
+// By output phase a = o mod 3 an output 3I + a reads tnr_up3_ntaps(a) LR neighbours per axis; neighbour t is LR pixel I + *d through
+// folded tap *k: a = 0: (I - 1, 4), (I, 1); a = 1: (I, 2); a = 2: (I, 3), (I + 1, 0).
+__host__ __device__ inline int tnr_up3_ntaps(int a) { return a == 1 ? 1 : 2; }
+__host__ __device__ inline void tnr_up3_phase_tap(int a, int t, int *d, int *k) {
+    if (a == 0) { *d = t - 1; *k = t == 0 ? 4 : 1; }
+    else if (a == 1) { *d = 0; *k = 2; }
+    else { *d = t; *k = t == 0 ? 3 : 0; }
+}
+
 // The fixed-order fp64 sum of a 256-thread block (`sh`: 256 doubles of LDS); the result is valid in thread 0.  Every reduction of
 // the library ends in it: two runs add in the same order and are bit-identical.
 __device__ __forceinline__ double tnr_block_sum256(double v, double *sh) {

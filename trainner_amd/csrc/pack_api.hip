@@ -90,6 +90,12 @@ extern "C" int tnr_pack_dims(int32_t Cout, int32_t Cin, int32_t kh, int32_t kw, 
             ko = tnr_round_up(Cin, 32); ki = tnr_round_up(Cout, TNR_CK);
             n = (int64_t)4 * ko * 4 * ki;
             break;
+        case TNR_PACK_UP3_FWD:
+        case TNR_PACK_UP3_DGRAD:      // fp32 fragments + the three bf16 planes of the 25 folded taps (csrc/conv_up3.hip)
+            TNR_REQUIRE(kh == 3 && kw == 3 && Cin == Cout && (Cin == 32 || Cin == 64), "pack up3: a 3x3 kernel over nf -> nf channels, nf 32 or 64 (got %d -> %d)", Cin, Cout);
+            ko = kind == TNR_PACK_UP3_FWD ? Cout : Cin; ki = kind == TNR_PACK_UP3_FWD ? Cin : Cout;
+            n = (int64_t)25 * ko * ki * 5 / 2;
+            break;
         default:
             tnr_set_error("pack: bad kind %d", kind);
             return TNR_EINVAL;
@@ -171,6 +177,63 @@ __global__ void pack_weights_kernel(const tnr_pack_item *items) {
             const int pp = vch / ki, co = vch - pp * ki;   // reduction channel = the 3x3 layer's output
             const int ky = 2 * (t >> 1) + (pp >> 1), kx = 2 * (t & 1) + (pp & 1);
             if (co < Cout && ci < Cin) v = tnr_upfold_tap(it.w + ((size_t)co * Cin + ci) * 9, ky, kx);
+        } else if (it.kind == TNR_PACK_UP3_FWD || it.kind == TNR_PACK_UP3_DGRAD) {
+            // step s = one folded tap x 16 reduced channels.  fp32 region: [s][8-group][lane half][row][4]; bf16 region behind it:
+            // [s][plane][lane half][row][8 bf16] -- a lane's A fragment of v_mfma_f32_32x32x2_f32 (x4) | v_mfma_f32_32x32x16_bf16 is 16 bytes
+            const bool fwd = it.kind == TNR_PACK_UP3_FWD;
+            const int ks_n = ki / 16;
+            const int64_t f32n = (int64_t)25 * ks_n * ko * 16;
+            int s, row, c0, plane = -1;
+            if (e < f32n) {
+                row = (int)((e >> 2) % ko);
+                const int64_t q = (e >> 2) / ko;      // (s, group, half)
+                s = (int)(q >> 2);
+                c0 = (int)((q >> 1) & 1) * 8 + (int)(q & 1) * 4 + (int)(e & 3);
+            } else {
+                const int64_t eb = e - f32n;
+                row = (int)((eb >> 2) % ko);
+                const int64_t q = (eb >> 2) / ko;     // (s, plane, half)
+                s = (int)(q / 6);
+                plane = (int)(q % 6) >> 1;
+                c0 = (int)(q & 1) * 8 + (int)(eb & 3) * 2;
+            }
+            int ky, kx, ks;
+            if (fwd) {                                // taps by output phase (a, b), inside a phase (ty, tx) ascending
+                ks = s % ks_n;
+                int t25 = s / ks_n, dy, dx;
+                ky = kx = 0;
+                for (int p = 0; p < 9; ++p) {
+                    const int na = tnr_up3_ntaps(p / 3), nb = tnr_up3_ntaps(p % 3);
+                    if (t25 < na * nb) {
+                        tnr_up3_phase_tap(p / 3, t25 / nb, &dy, &ky);
+                        tnr_up3_phase_tap(p % 3, t25 % nb, &dx, &kx);
+                        break;
+                    }
+                    t25 -= na * nb;
+                }
+            } else {                                  // chunks of 16 reduced channels, inside a chunk the taps ky * 5 + kx
+                ks = s / 25;
+                ky = (s % 25) / 5; kx = (s % 25) % 5;
+            }
+            auto tap = [&](int c) {                   // row = produced channel, c = reduced channel
+                const int co = fwd ? row : c, ci = fwd ? c : row;
+                return tnr_up3fold_tap(it.w + ((size_t)co * Cin + ci) * 9, ky, kx);
+            };
+            if (plane < 0) {
+                v = tap(ks * 16 + c0);
+            } else {
+                unsigned short b[2];
+                for (int j = 0; j < 2; ++j) {
+                    float r = tap(ks * 16 + c0 + j);
+                    __bf16 h = (__bf16)r;
+                    for (int l = 0; l < plane; ++l) {
+                        r = r - (float)h;
+                        h = (__bf16)r;
+                    }
+                    b[j] = __builtin_bit_cast(unsigned short, h);
+                }
+                v = __builtin_bit_cast(float, (unsigned)b[0] | ((unsigned)b[1] << 16));
+            }
         } else {  // TNR_PACK_DGRAD_S2: [par][t][ci][co]
             const int co = (int)(e % ki);
             int64_t q = e / ki;
@@ -243,6 +306,16 @@ extern "C" int tnr_upconv_fold_table(int32_t out[144]) {
         for (int t = 0; t < 9; ++t) {
             const int ky = k >> 2, kx = k & 3, ty = t / 3, tx = t % 3;
             out[k * 9 + t] = ty >= tnr_upfold_lo(ky) && ty <= tnr_upfold_hi(ky) && tx >= tnr_upfold_lo(kx) && tx <= tnr_upfold_hi(kx);
+        }
+    return TNR_OK;
+}
+
+extern "C" int tnr_upconv3_fold_table(int32_t out[225]) {
+    TNR_REQUIRE(out != nullptr, "upconv3_fold_table: null pointer");
+    for (int k = 0; k < 25; ++k)
+        for (int t = 0; t < 9; ++t) {
+            const int ky = k / 5, kx = k % 5, ty = t / 3, tx = t % 3;
+            out[k * 9 + t] = ty >= tnr_up3fold_lo(ky) && ty <= tnr_up3fold_hi(ky) && tx >= tnr_up3fold_lo(kx) && tx <= tnr_up3fold_hi(kx);
         }
     return TNR_OK;
 }

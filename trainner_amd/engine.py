@@ -12,8 +12,18 @@ class ConvOp:
     """Forward, data-gradient and weight-gradient launches of one Conv2dHIP layer."""
 
     def __init__(self, mod, packer, need_dgrad=True, ups=False):
+        """ups: False, True (nearest x2 in front of the layer) or 3 (nearest x3: the layer's only form is csrc/conv_up3.hip)."""
         self.mod, self.packer = mod, packer
         k, s = mod.kernel_size, mod.stride
+        self.up3 = ups == 3
+        if self.up3:
+            if k != 3 or s != 1 or mod.in_channels != mod.out_channels or mod.in_channels not in (32, 64):
+                raise NotImplementedError("x3 up-conv layer: a 3x3 stride-1 conv of nf -> nf channels, nf 32 or 64 (got %d -> %d)"
+                                          % (mod.in_channels, mod.out_channels))
+            self.ups = 3
+            self.i_f = packer.add(mod.weight, ops.PACK_UP3_FWD)
+            self.i_d = packer.add(mod.weight, ops.PACK_UP3_DGRAD) if need_dgrad else None
+            return
         if k == 3 and s == 1:
             self.mode_f = ops.CONV_3x3_UP2 if ups else ops.CONV_3x3
             self.mode_d = ops.CONV_3x3
@@ -64,7 +74,9 @@ class ConvOp:
 
     def fwd_up2(self, x, y, **epi):
         """An UP2 layer's forward in the form ops.upconv_plan names: folded, one four-tap stride-2 data-gradient launch over the folded
-        weights (bias, activation and slope as in fwd); else fwd itself, the TNR_CONV_3x3_UP2 launch."""
+        weights (bias, activation and slope as in fwd); else fwd itself, the TNR_CONV_3x3_UP2 launch.  An x3 layer: tnr_upconv3_fwd."""
+        if self.up3:
+            return ops.upconv3_fwd(x, self.packer.get(self.i_f), y, bias=self.mod.bias, **epi)
         if "fwd" not in ops.upconv_plan(x)[0]:
             return self.fwd(x, y, **epi)
         ops.conv(x, self.packer.get(self.i_uf), y, mode=ops.DGRAD_4x4_S2, family=ops.UPFOLD_FAMILY, bias=self.mod.bias, **epi)
@@ -86,7 +98,9 @@ class ConvOp:
     def dgrad_up2(self, g, gx, mask=None, m_slope=0.2):
         """An UP2 layer's gradient in the LOW-resolution domain: gx = the 2 x 2 block sums of conv_transpose(g), times LeakyReLU'(mask)
         where the layer's input is an activation's output.  Folded: one four-tap stride-2 launch with the mask in its epilogue; else
-        the 3x3 data-gradient into a high-resolution scratch and tnr_upsample2x_bwd."""
+        the 3x3 data-gradient into a high-resolution scratch and tnr_upsample2x_bwd.  An x3 layer: tnr_upconv3_dgrad, the 3 x 3 block sums."""
+        if self.up3:
+            return ops.upconv3_dgrad(g, self.packer.get(self.i_d), gx, mask=mask, m_slope=m_slope)
         if "dgrad" in ops.upconv_plan(gx)[0]:
             epi = dict(mask=mask, m_slope=m_slope) if mask is not None else {}
             ops.conv(g, self.packer.get(self.i_ud), gx, mode=ops.CONV_4x4_S2, family=ops.UPFOLD_FAMILY, **epi)
@@ -118,6 +132,9 @@ class ConvOp:
         return dict(x=x, g=g, dw=w.grad, db=db, cin_begin=cin_begin, alpha=alpha, beta=1.0, reflect=reflect)
 
     def wgrad(self, x, g, alpha=1.0, cin_begin=0, with_bias=True, reflect=False):
+        if self.up3:
+            m = self.mod
+            return ops.upconv3_wgrad(x, g, m.weight.grad, m.bias.grad if (with_bias and m.bias is not None) else None, alpha=alpha, beta=1.0)
         if self.ups and cin_begin == 0 and not reflect and "wgrad" in ops.upconv_plan(x)[0]:
             self._wgrad_up2_folded(x, g, alpha, with_bias)
             return

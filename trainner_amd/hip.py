@@ -23,6 +23,7 @@ PACK_FWD, PACK_DGRAD_3x3, PACK_FWD_S2D, PACK_DGRAD_S2, PACK_COL_FWD, PACK_COL_DG
 PACK_C4_FWD, PACK_C4_DGRAD3 = 6, 7
 PACK_UP2_DGRAD_S2, PACK_UP2_FWD_S2D = 8, 9      # a nearest-x2 3x3 layer folded into its virtual 4x4 stride-2 convolution
 PACK_UNSHUFFLE_FWD = 10                         # the fea layer behind a pixel unshuffle: its (3s) x (3s) stride-s window over the image
+PACK_UP3_FWD, PACK_UP3_DGRAD = 11, 12           # a nearest-x3 3x3 layer as its 25 folded taps, ready matrix-core fragments (csrc/conv_up3.hip)
 PACK_DENSE_DGRAD = 16      # host-side tag of tnr_pack_dense_dgrad slabs (consumed like PACK_FWD by conv_tile)
 
 
@@ -112,6 +113,11 @@ _SIGS = {
     "tnr_conv_unshuffle_fwd": (c_i, [CView, c_i, c_i, c_i, c_p, CView, c_i, c_i, c_p, c_i, c_p]),
     "tnr_wgrad_unshuffle_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i]),
     "tnr_wgrad_unshuffle": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_l, c_p]),
+    "tnr_upconv3_fold_table": (c_i, [C.POINTER(c_i * 225)]),
+    "tnr_upconv3_fwd": (c_i, [CView, c_i, c_i, c_i, c_p, CView, c_i, c_p, c_i, c_f, c_i, c_p]),
+    "tnr_upconv3_dgrad": (c_i, [CView, c_i, c_i, c_i, c_p, CView, c_i, CView, c_f, c_i, c_p]),
+    "tnr_upconv3_wgrad_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i]),
+    "tnr_upconv3_wgrad": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_p, c_f, c_f, c_p, c_l, c_p]),
     "tnr_conv_wgrad": (c_i, [C.POINTER(WgradDesc), c_p]),
     "tnr_conv_wgrad_group": (c_i, [C.POINTER(WgradDesc), c_i, c_p]),
     "tnr_wgrad_tile_class": (c_i, [C.POINTER(WgradDesc), c_i, C.POINTER(c_i * 12)]),

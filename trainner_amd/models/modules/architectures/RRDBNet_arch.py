@@ -69,8 +69,18 @@ class RRDBNet(HipNet):
             raise NotImplementedError("RRDBNet option outside the ESRGAN recipe is not implemented by the HIP engine")
         if plus and nf not in (32, 64):
             raise NotImplementedError("RRDBNet plus: the weight-space fold (csrc/dense_plus.hip) is built for nf 32 and 64")
-        if upscale not in (2, 4, 8) or upsample_mode not in ("upconv", "pixelshuffle"):
+        if upscale not in (2, 3, 4, 8) or upsample_mode not in ("upconv", "pixelshuffle"):
             raise NotImplementedError("upscale %s / upsample mode [%s] is not found" % (upscale, upsample_mode))
+        # upscale 3 (:20-21, :35-36): ONE up-conv stage of nearest x3 + conv + act; the layer runs as its folded 5x5 stride-3 transposed
+        # convolution (csrc/conv_up3.hip), which is built for the up-conv form and nf 32 / 64 only
+        if upscale == 3 and upsample_mode != "upconv":
+            raise NotImplementedError("RRDBNet upscale 3 with upsample_mode [pixelshuffle] (a 9 nf-channel conv + PixelShuffle(3)) is not implemented by "
+                                      "the HIP engine: the x3 layer is built for upsample_mode upconv")
+        if upscale == 3 and in_nc in (12, 48):
+            raise NotImplementedError("RRDBNet upscale 3 behind a pixel unshuffle (use_unshuffle with a scale-3 network, in_nc %d) is not implemented "
+                                      "by the HIP engine: the unshuffle models keep the x4 network" % in_nc)
+        if upscale == 3 and nf not in (32, 64):
+            raise NotImplementedError("RRDBNet upscale 3: the x3 up-conv layer is built for nf 32 and 64 (got nf %d)" % nf)
         # in_nc 12 / 48: the RGB image behind a pixel unshuffle of 2 / 4 (use_unshuffle: the x2 and x1 models keep the x4 network).  The
         # first layer keeps the reference's [nf, in_nc, 3, 3] weight and reads the image itself (engine.UnshuffleConvOp).
         self.unshuffle = {12: 2, 48: 4}.get(in_nc, 0)
@@ -83,7 +93,8 @@ class RRDBNet(HipNet):
             raise NotImplementedError("HIP RRDBNet needs nf %% 32 == 0 and in_nc <= 3 (or 12 / 48: RGB behind a pixel unshuffle of 2 / 4), "
                                       "got in_nc %d" % in_nc)
         self.in_nc, self.out_nc, self.nf, self.nb, self.gc = in_nc, out_nc, nf, nb, 32  # reference ignores gc (:24)
-        self.upsample_mode, self.n_up = upsample_mode, int(math.log(upscale, 2))
+        self.up_factor = 3 if upscale == 3 else 2
+        self.upsample_mode, self.n_up = upsample_mode, 1 if upscale == 3 else int(math.log(upscale, 2))
         self.act, self.slope = B.act_code(act_type)
         # ESRGAN+ GaussianNoise at the end of every dense block (ResidualDenseBlock_5C.forward :160-163, block.py:587-600: sigma 0.1,
         # training mode only, gradient through both terms; on by default, options/defaults.py:59).  The draw is a counter-based
@@ -102,7 +113,7 @@ class RRDBNet(HipNet):
         ups = []
         for _ in range(self.n_up):
             if upsample_mode == "upconv":
-                ups.append(B.flat_sequential(B.Marker("nearest x2"), B.conv_block(nf, nf, 3, act_type=act_type)))
+                ups.append(B.flat_sequential(B.Marker("nearest x%d" % self.up_factor), B.conv_block(nf, nf, 3, act_type=act_type)))
             else:
                 ups.append(B.flat_sequential(B.conv_block(nf, nf * 4, 3, act_type=None), B.Marker("pixelshuffle x2"),
                                              B.Marker("act:" + act_type)))
@@ -137,7 +148,7 @@ class RRDBNet(HipNet):
         idx = 2
         for _ in range(self.n_up):
             if self.upsample_mode == "upconv":
-                o["up"].append(ConvOp(m[idx + 1], packer, ups=True))
+                o["up"].append(ConvOp(m[idx + 1], packer, ups=3 if self.up_factor == 3 else True))
             else:
                 o["up"].append(ConvOp(m[idx], packer))
             idx += 3
@@ -193,7 +204,7 @@ class RRDBNet(HipNet):
         o["lr"].fwd(View(trunk), View(y0), r1=fea_keep)          # ShortcutBlock: fea + trunk(fea)
         cur, stages = View(y0), []
         for u in o["up"]:
-            H2, W2 = cur.H * 2, cur.W * 2
+            H2, W2 = cur.H * self.up_factor, cur.W * self.up_factor
             if self.upsample_mode == "upconv":
                 nxt = View(new_act(N, H2, W2, nf, dev))
                 u.fwd_up2(cur, nxt, act=act, slope=sl)

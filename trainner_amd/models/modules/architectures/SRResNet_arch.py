@@ -28,6 +28,9 @@ class SRResNet(HipNet):
         super().__init__()
         if norm_type is not None or mode != "CNA" or convtype != "Conv2D" or finalact or res_scale != 1:
             raise NotImplementedError("SRResNet option outside the default recipe is not implemented by the HIP engine")
+        if upscale == 3:      # (SRResNet_arch.py:33-34: one PixelShuffle(3) stage)
+            raise NotImplementedError("SRResNet upscale 3 (a PixelShuffle(3) stage) is not implemented by the HIP engine: scale 3 is built for "
+                                      "RRDBNet's up-conv layer")
         if upsample_mode != "pixelshuffle" or upscale not in (2, 4, 8):
             raise NotImplementedError("upsample mode [%s] is not implemented by the HIP SRResNet" % upsample_mode)
         if nf % 32 or in_nc > 4 or out_nc > 4:

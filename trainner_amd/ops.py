@@ -12,7 +12,7 @@ import torch
 from . import hip
 from .hip import (ACT_LRELU, ACT_NONE, ACT_RELU, CONV_1x1, CONV_3x3, CONV_3x3_C4, CONV_3x3_UP2, CONV_4x4_S2, CONV_7x7_C4, DGRAD_4x4_S2,  # noqa: F401
                   PACK_C4_DGRAD3, PACK_C4_FWD, PACK_COL_DGRAD3, PACK_COL_FWD, PACK_DENSE_DGRAD, PACK_DGRAD_3x3, PACK_DGRAD_S2, PACK_FWD, PACK_FWD_S2D, PACK_UP2_DGRAD_S2,
-                  PACK_UNSHUFFLE_FWD, PACK_UP2_FWD_S2D, CView,
+                  PACK_UNSHUFFLE_FWD, PACK_UP2_FWD_S2D, PACK_UP3_DGRAD, PACK_UP3_FWD, CView,
                   ConvDesc,
                   DensePackItem, PackItem, WgradDesc)
 
@@ -811,6 +811,89 @@ def upconv_wgrad_unfold(dws, dw3, alpha=1.0, beta=1.0):
     Cout, Cin = dw3.shape[0], dw3.shape[1]
     assert tuple(dws.shape) == (Cin, Cout, 4, 4) and dws.is_contiguous() and dw3.is_contiguous()
     hip.check(hip.load().tnr_upconv_wgrad_unfold(dws.data_ptr(), dw3.data_ptr(), Cout, Cin, alpha, beta, hip.stream()), "upconv_wgrad_unfold")
+
+
+# ----------------------------------------------------------------------------------------------
+# nearest x3 + 3x3 (RRDBNet upscale 3) as the transposed 5x5 stride-3 padding-1 convolution of the LR tensor (csrc/conv_up3.hip)
+# ----------------------------------------------------------------------------------------------
+UP3_FAMILY = "conv_up3"                 # PROFILE family of the three launches, counted with the FLOP they execute (25 taps per LR pixel)
+# per axis: the 3x3 taps summed into folded tap k = 0..4 (csrc/common.h tnr_up3fold_lo / tnr_up3fold_hi); LR pixel i reaches output 3i - 1 + k
+UP3FOLD_TAPS = ((2,), (1, 2), (0, 1, 2), (0, 1), (0,))
+
+
+def upconv3_fold_table():
+    """The library's 25 x 9 fold matrix (tnr_upconv3_fold_table) as a float64 tensor: row ky*5 + kx, column ty*3 + tx."""
+    out = (C.c_int32 * 225)()
+    hip.check(hip.load().tnr_upconv3_fold_table(C.byref(out)), "upconv3_fold_table")
+    return torch.tensor(list(out), dtype=torch.float64).view(25, 9)
+
+
+def _sum_asc(terms):
+    out = terms[0]
+    for t in terms[1:]:
+        out = out + t
+    return out
+
+
+def upconv3_fold_weights(w):
+    """[..., 3, 3] -> the folded [..., 5, 5] taps in the library's order (tnr_up3fold_tap): inside a row over ascending kx first, then
+    the row sums over ascending ky.  F.conv_transpose2d(x, fold(w).transpose(0, 1), stride=3, padding=1) IS the layer."""
+    rows = [torch.stack([_sum_asc([w[..., ty, tx] for tx in t]) for t in UP3FOLD_TAPS], dim=-1) for ty in range(3)]
+    return torch.stack([_sum_asc([rows[ty] for ty in t]) for t in UP3FOLD_TAPS], dim=-2)
+
+
+def upconv3_unfold_grad(dK):
+    """[..., 5, 5] gradients of the folded taps -> [..., 3, 3] (the transpose of the fold): 3x3 tap t collects folded taps 2 - t .. 4 - t
+    per axis, added in ascending (ky, kx) as the reduce launch of tnr_upconv3_wgrad does."""
+    return torch.stack([torch.stack([_sum_asc([dK[..., ky, kx] for ky in range(2 - ty, 5 - ty) for kx in range(2 - tx, 5 - tx)])
+                                     for tx in range(3)], dim=-1) for ty in range(3)], dim=-2)
+
+
+def _up3_check(who, wp, kind, lo, hi):
+    if wp.kind != kind or wp.KoutP != lo.C or wp.KinP != lo.C or hi.C != lo.C or lo.C not in (32, 64):
+        raise hip.HipEngineError("%s: the x3 up-conv layer is built for nf 32 and 64 with its own packing (got %d -> %d channels, pack kind %d)"
+                                 % (who, lo.C, hi.C, wp.kind))
+    if (hi.N, hi.H, hi.W) != (lo.N, 3 * lo.H, 3 * lo.W):
+        raise hip.HipEngineError("%s: %s is not the x3 extent of %s" % (who, tuple(hi.buf.shape), tuple(lo.buf.shape)))
+
+
+def upconv3_fwd(x, wp, y, bias=None, act=ACT_NONE, slope=0.2):
+    """y [N, 3H, 3W, nf] = act(conv3x3(nearest_x3(x)) + bias) in one launch over the LR view x (tnr_upconv3_fwd); wp: the layer's
+    PACK_UP3_FWD image.  Arithmetic: ops.MMA."""
+    _up3_check("upconv3_fwd", wp, PACK_UP3_FWD, x, y)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(hip.load().tnr_upconv3_fwd(x.c(), x.N, x.H, x.W, wp.t.data_ptr(), y.c(), x.C, hip.ptr(bias), act, slope, MMA, hip.stream()),
+              "upconv3_fwd")
+    if PROFILE is not None:
+        PROFILE.end(UP3_FAMILY, 2.0 * x.pixels * 25 * x.C * x.C, t0, (x.C, x.C, x.H, 0))
+
+
+def upconv3_dgrad(g, wp, gx, mask=None, m_slope=0.2):
+    """gx [N, H, W, nf] = the layer's data gradient in the LR domain from g [N, 3H, 3W, nf] (already times the layer's own LeakyReLU'),
+    times LeakyReLU'(mask) when the layer's input is an activation's output (tnr_upconv3_dgrad); wp: the PACK_UP3_DGRAD image."""
+    _up3_check("upconv3_dgrad", wp, PACK_UP3_DGRAD, gx, g)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(hip.load().tnr_upconv3_dgrad(g.c(), gx.N, gx.H, gx.W, wp.t.data_ptr(), gx.c(), gx.C, cv(mask), m_slope, MMA, hip.stream()),
+              "upconv3_dgrad")
+    if PROFILE is not None:
+        PROFILE.end(UP3_FAMILY, 2.0 * gx.pixels * 25 * gx.C * gx.C, t0, (gx.C, gx.C, gx.H, 1))
+
+
+def upconv3_wgrad(x, g, dw, db=None, alpha=1.0, beta=1.0):
+    """dw [nf, nf, 3, 3] = beta dw + alpha * the layer's weight gradient from the LR input x and g (tnr_upconv3_wgrad: 25 folded-tap
+    products, then the 25 -> 9 unfold; deterministic); db likewise from tnr_bias_grad (may be None)."""
+    if x.C != g.C or x.C not in (32, 64) or (g.N, g.H, g.W) != (x.N, 3 * x.H, 3 * x.W) or tuple(dw.shape) != (x.C, x.C, 3, 3) or not dw.is_contiguous():
+        raise hip.HipEngineError("upconv3_wgrad: an nf -> nf layer, nf 32 or 64, g at three times the extent of x")
+    lib = hip.load()
+    need = lib.tnr_upconv3_wgrad_workspace_bytes(x.N, x.H, x.W, x.C)
+    ws = WS.get("upconv3_wgrad@%x" % hip.stream(), need, x.buf.device)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(lib.tnr_upconv3_wgrad(x.c(), g.c(), x.N, x.H, x.W, x.C, dw.data_ptr(), alpha, beta, ws.data_ptr(), ws.numel() * 8, hip.stream()),
+              "upconv3_wgrad")
+    if PROFILE is not None:
+        PROFILE.end(UP3_FAMILY, 2.0 * x.pixels * 25 * x.C * x.C, t0, (x.C, x.C, x.H, 2))
+    if db is not None:
+        bias_grad(g, db, alpha=alpha, beta=beta)
 
 
 CHAIN_MAX = 6
