@@ -405,6 +405,27 @@ int tnr_upconv3_dgrad(tnr_view g, int32_t N, int32_t H, int32_t W, const float *
 int64_t tnr_upconv3_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t nf);
 int tnr_upconv3_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H, int32_t W, int32_t nf, float *dw, float alpha, float beta, float *ws,
                       int64_t ws_bytes, void *stream);
+/* The image-to-image decoders' up-conv layer (upsample_mode: upconv -- nn.Upsample(scale_factor=2, nearest) + Conv2d(Cin, Cout, 3, 1, 1), no
+ * activation; ResNet_arch.py:80-83, UNet_arch.py:119-146) as the transposed 4x4 stride-2 padding-1 convolution of the LOW-resolution tensor
+ * over the 16 folded taps (tnr_upconv_fold_table), csrc/conv_upconv_i2i.hip.  The up-sampled tensor never exists.  Cin, Cout: multiples of
+ * 4, 4 <= Cout <= 512, 4 <= Cin <= 2048; x, gx: [N, H, W, Cin] views; y, g: [N, 2H, 2W, Cout] views; mma: TNR_MMA_*.
+ *   tnr_upconv_i2i_pack : the layer's weight w [Cout][Cin][3][3] as ready matrix-core fragments of `mma` in consumption order, dgrad = 0: the
+ *                         forward image, 1: the data-gradient image; `out` holds tnr_upconv_i2i_pack_floats(...) floats, 16-byte aligned.
+ *   tnr_upconv_i2i_fwd  : y = conv + bias (bias may be NULL); a workgroup stages 32 channels of an 8 x 16 LR tile + halo at a time and feeds
+ *                         all four output parities from it.
+ *   tnr_upconv_i2i_dgrad: gx[i, j] = sum_k F[k]^T g[2i - 1 + ky, 2j - 1 + kx], in the LR domain directly.
+ *   tnr_upconv_i2i_wgrad: dw[co][ci][3][3] = beta dw + alpha unfold(dF), dF[k][ci][co] = sum over LR pixels of x (x) g of the tap's parity:
+ *                         fp32 matrix-core products, partial slabs in ws (tnr_upconv_i2i_wgrad_workspace_bytes) added in a fixed order and
+ *                         unfolded (3x3 tap t <- folded taps 2 - t, 3 - t per axis) by a second launch.  Deterministic.  db: tnr_bias_grad. */
+int64_t tnr_upconv_i2i_pack_floats(int32_t Cout, int32_t Cin, int32_t dgrad, int32_t mma);
+int tnr_upconv_i2i_pack(const float *w, int32_t Cout, int32_t Cin, int32_t dgrad, int32_t mma, float *out, int64_t out_floats, void *stream);
+int tnr_upconv_i2i_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *wp, tnr_view y, int32_t Cout, const float *bias,
+                       int32_t mma, void *stream);
+int tnr_upconv_i2i_dgrad(tnr_view g, int32_t N, int32_t H, int32_t W, int32_t Cout, const float *wp, tnr_view gx, int32_t Cin, int32_t mma,
+                         void *stream);
+int64_t tnr_upconv_i2i_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
+int tnr_upconv_i2i_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, float *dw, float alpha, float beta,
+                         float *ws, int64_t ws_bytes, void *stream);
 int tnr_conv_wgrad(const tnr_wgrad_desc *d, void *stream);
 /* n <= TNR_WGRAD_GROUP_MAX layers in ONE launch (+ one reduce launch).  The layers must share mode and
  * N/H/W/Ho/Wo and fall into the same workgroup tile class (same Cout <= 32 | > 32 and the same number of

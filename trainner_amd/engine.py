@@ -153,6 +153,50 @@ class ConvOp:
         ops.wgrad_group([self.wgrad_item(x, g, alpha, cin_begin, with_bias)], mode=self.mode_f)
 
 
+class UpConvI2IOp:
+    """Upsample(nearest x2) + Conv2dHIP(Cin, Cout, 3, 1) of an image-to-image decoder (upsample_mode: upconv) on csrc/conv_upconv_i2i.hip:
+    forward, data gradient in the LR domain and weight gradient, one launch family each.  A produced channel count that is not a multiple
+    of 4 (the image) is zero-extended through a shadow copy (re-filled whenever the parameters change; the gradient comes back through it)."""
+
+    def __init__(self, mod):
+        if mod.kernel_size != 3 or mod.stride != 1:
+            raise NotImplementedError("up-conv layer: a 3x3 stride-1 convolution (got k=%d s=%d)" % (mod.kernel_size, mod.stride))
+        self.mod = mod
+        w, O = mod.weight, mod.out_channels
+        self.opad = (O + 3) // 4 * 4
+        self.w, self.dw, self.bias_pad = w, None, None
+        if self.opad != O:
+            self.w = torch.zeros((self.opad,) + tuple(w.shape[1:]), dtype=torch.float32, device=w.device)
+            self.dw = torch.zeros_like(self.w)
+            self.bias_pad = torch.zeros(self.opad, dtype=torch.float32, device=w.device) if mod.bias is not None else None
+        self.wts = ops.UpconvI2IWeights(self.w)
+
+    def refresh(self):
+        O = self.mod.out_channels
+        if self.opad != O:
+            self.w[:O].copy_(self.mod.weight.detach())
+            if self.bias_pad is not None:
+                self.bias_pad[:O].copy_(self.mod.bias.detach())
+        self.wts.pack()
+
+    def fwd(self, x_small, y_large):
+        ops.upconv_i2i_fwd(x_small, self.wts, y_large, bias=self.mod.bias if self.dw is None else self.bias_pad)
+
+    def bwd_data(self, g_large, g_small):
+        ops.upconv_i2i_dgrad(g_large, self.wts, g_small)
+
+    def wgrad(self, g_large, x_small):
+        m, O = self.mod, self.mod.out_channels
+        if self.dw is None:
+            ops.upconv_i2i_wgrad(x_small, g_large, m.weight.grad, m.bias.grad if m.bias is not None else None, beta=1.0)
+            return
+        db = torch.zeros(self.opad, dtype=torch.float32, device=self.dw.device) if m.bias is not None else None
+        ops.upconv_i2i_wgrad(x_small, g_large, self.dw, db, beta=0.0)
+        m.weight.grad.add_(self.dw[:O])
+        if db is not None:
+            m.bias.grad.add_(db[:O])
+
+
 class UnshuffleConvOp:
     """A generator's first 3x3 layer behind a pixel unshuffle of s (in_channels = 3 s^2): forward and weight gradient read the NHWC4
     image itself through the layer's (3s) x (3s) stride-s window (csrc/conv_unshuffle.hip).  The input is the image: no data gradient."""

@@ -118,6 +118,12 @@ _SIGS = {
     "tnr_upconv3_dgrad": (c_i, [CView, c_i, c_i, c_i, c_p, CView, c_i, CView, c_f, c_i, c_p]),
     "tnr_upconv3_wgrad_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i]),
     "tnr_upconv3_wgrad": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_p, c_f, c_f, c_p, c_l, c_p]),
+    "tnr_upconv_i2i_pack_floats": (c_l, [c_i, c_i, c_i, c_i]),
+    "tnr_upconv_i2i_pack": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_l, c_p]),
+    "tnr_upconv_i2i_fwd": (c_i, [CView, c_i, c_i, c_i, c_i, c_p, CView, c_i, c_p, c_i, c_p]),
+    "tnr_upconv_i2i_dgrad": (c_i, [CView, c_i, c_i, c_i, c_i, c_p, CView, c_i, c_i, c_p]),
+    "tnr_upconv_i2i_wgrad_workspace_bytes": (c_l, [c_i, c_i, c_i, c_i, c_i]),
+    "tnr_upconv_i2i_wgrad": (c_i, [CView, CView, c_i, c_i, c_i, c_i, c_i, c_p, c_f, c_f, c_p, c_l, c_p]),
     "tnr_conv_wgrad": (c_i, [C.POINTER(WgradDesc), c_p]),
     "tnr_conv_wgrad_group": (c_i, [C.POINTER(WgradDesc), c_i, c_p]),
     "tnr_wgrad_tile_class": (c_i, [C.POINTER(WgradDesc), c_i, C.POINTER(c_i * 12)]),

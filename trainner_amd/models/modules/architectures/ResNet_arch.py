@@ -2,7 +2,8 @@
 
 Constructor, `state_dict` keys and arithmetic follow codes/models/modules/architectures/ResNet_arch.py:11-149:
 ReflectionPad(3) + conv7x7(in -> ngf) + norm + ReLU; two conv3x3 stride 2 + norm + ReLU; n_blocks x [x + (ReflectionPad(1) +
-conv3x3 + norm + ReLU + ReflectionPad(1) + conv3x3 + norm)]; two ConvTranspose2d(k3, s2, p1, output_padding 1) + norm + ReLU;
+conv3x3 + norm + ReLU + ReflectionPad(1) + conv3x3 + norm)]; two ConvTranspose2d(k3, s2, p1, output_padding 1) + norm + ReLU
+(upsample_mode "upconv": two nn.Sequential(Upsample(nearest x2), conv3x3) in their place, block.upconv_block with act_type None);
 ReflectionPad(3) + conv7x7(ngf -> out) + Tanh.  norm = InstanceNorm2d (no affine, no running statistics; convolutions
 then carry a bias) or BatchNorm2d (train mode).  `self.model` is an nn.Sequential with the reference's child indices.
 
@@ -19,6 +20,8 @@ Kernel mapping (all fp32 NHWC):
     tnr_wgrad_thin7 towards the image side, reflection applied where the operand is gathered (no padded copy of a wide tensor);
     TNR_K7_FUSED=0 keeps the earlier form, nine 3x3 blocks of taps over shifted copies of the 4-channel operand (A/B switch);
     the generic kernels of csrc/gconv.hip are the fallback for channel counts those kernels do not take;
+  * upsample_mode "upconv": the two up-sampling layers run on csrc/conv_upconv_i2i.hip (engine.UpConvI2IOp): the transposed 4x4 stride-2
+    convolution of the low-resolution tensor over the 16 folded taps, all three passes; the up-sampled tensor is never stored;
   * normalisation: the BatchNorm-train kernels (InstanceNorm: one statistics group per image in the same launches:
     tnr_instnorm_*), ReLU fused; Tanh as one pass.
 """
@@ -28,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from .... import ops
-from ....engine import ConvOp, HipNet
+from ....engine import ConvOp, HipNet, UpConvI2IOp
 from ....ops import View, new_act
 from . import block as B
 
@@ -242,11 +245,12 @@ class ResnetGenerator(HipNet):
             norm = "instance"
         else:
             raise NameError("Unknown norm layer")
-        if use_dropout or padding_type != "reflect" or upsample_mode != "deconv":
-            raise NotImplementedError("HIP ResnetGenerator implements reflect padding, deconv up-sampling, no dropout")
+        if use_dropout or padding_type != "reflect" or upsample_mode not in ("deconv", "upconv"):
+            raise NotImplementedError("HIP ResnetGenerator implements reflect padding, deconv | upconv up-sampling, no dropout")
         if input_nc > 4 or output_nc > 4 or ngf % 8:
             raise NotImplementedError("HIP ResnetGenerator needs <= 4 image channels and ngf %% 8 == 0")
         self.input_nc, self.output_nc, self.ngf, self.norm, self.n_blocks = input_nc, output_nc, ngf, norm, n_blocks
+        self.upsample_mode = upsample_mode
         ub = norm == "instance"                                   # use_bias (ResNet_arch.py:47-50)
         m = [B.Marker("reflectpad3"), B.Conv2dHIP(input_nc, ngf, 7, 1, bias=ub), _norm_module(norm, ngf), B.Marker("act:relu")]
         for i in range(2):
@@ -256,7 +260,11 @@ class ResnetGenerator(HipNet):
             m.append(ResnetBlock(ngf * 4, norm, ub))
         for i in range(2):
             mult = 2 ** (2 - i)
-            m += [ConvTranspose2dHIP(ngf * mult, ngf * mult // 2, 3, 2, bias=ub), _norm_module(norm, ngf * mult // 2), B.Marker("act:relu")]
+            if upsample_mode == "deconv":
+                up = ConvTranspose2dHIP(ngf * mult, ngf * mult // 2, 3, 2, bias=ub)
+            else:           # block.upconv_block(act_type=None): Sequential(Upsample, Conv2d), the parameters under child 1
+                up = nn.Sequential(B.Marker("upsample:nearest2"), B.Conv2dHIP(ngf * mult, ngf * mult // 2, 3, 1, bias=ub))
+            m += [up, _norm_module(norm, ngf * mult // 2), B.Marker("act:relu")]
         m += [B.Marker("reflectpad3"), B.Conv2dHIP(ngf, output_nc, 7, 1, bias=True), B.Marker("tanh")]
         self.model = nn.Sequential(*m)
         self._init_engine()
@@ -270,8 +278,12 @@ class ResnetGenerator(HipNet):
         self._k7 = (_K7Image(self._c_in, packer, "in"), _K7Image(self._c_out, packer, "out")) if (self.ngf in (16, 32, 64) and self.input_nc <= 3 and self.output_nc <= 3) else None
         self._downs = [_Padded4x4(m[4].weight, packer, False), _Padded4x4(m[7].weight, packer, False)]
         self._down_mods = [m[4], m[7]]
-        self._ups = [_Padded4x4(m[10 + nb].weight, packer, True), _Padded4x4(m[13 + nb].weight, packer, True)]
-        self._up_mods = [m[10 + nb], m[13 + nb]]
+        if self.upsample_mode == "upconv":
+            self._up_mods = [m[10 + nb][1], m[13 + nb][1]]
+            self._ups = [UpConvI2IOp(mod) for mod in self._up_mods]
+        else:
+            self._ups = [_Padded4x4(m[10 + nb].weight, packer, True), _Padded4x4(m[13 + nb].weight, packer, True)]
+            self._up_mods = [m[10 + nb], m[13 + nb]]
         self._norms = {"in": m[2], "d0": m[5], "d1": m[8], "u0": m[11 + nb], "u1": m[14 + nb]}
         self._blocks = []
         for i in range(nb):
@@ -354,7 +366,10 @@ class ResnetGenerator(HipNet):
             cur = out
         for i, (p4, mod) in enumerate(zip(self._ups, self._up_mods)):
             z = View(new_act(N, cur.H * 2, cur.W * 2, mod.out_channels, dev))
-            p4.conv_t(cur, z, bias=mod.bias)
+            if self.upsample_mode == "upconv":
+                p4.fwd(cur, z)                                         # (+ bias)
+            else:
+                p4.conv_t(cur, z, bias=mod.bias)
             a = View(new_act(N, z.H, z.W, z.C, dev))
             tape["u%d" % i] = (cur, z, a, self._norm_fwd(self._norms["u%d" % i], z, a, R))
             cur = a
@@ -403,11 +418,16 @@ class ResnetGenerator(HipNet):
             p4, mod = self._ups[i], self._up_mods[i]
             gz = View(new_act(N, z.H, z.W, z.C, dev))
             self._norm_bwd(self._norms["u%d" % i], st, g, a, z, gz, True, Wg)
+            g = View(new_act(N, xin.H, xin.W, xin.C, dev))
+            if self.upsample_mode == "upconv":
+                if Wg:
+                    p4.wgrad(gz, xin)                              # (+ bias gradient)
+                p4.bwd_data(gz, g)
+                continue
             if Wg:
                 p4.wgrad(gz, xin)                                  # roles swapped: the virtual convolution maps large -> small
                 if mod.bias is not None:
                     ops.bias_grad(gz, mod.bias.grad)
-            g = View(new_act(N, xin.H, xin.W, xin.C, dev))
             p4.conv(gz, g)
         # residual blocks
         for bi in range(len(blocks) - 1, -1, -1):

@@ -14,14 +14,16 @@ the second half -- no torch.cat.
 Kernel mapping (all fp32 NHWC): every convolution is the 4x4 stride-2 space-to-depth MFMA kernel; a ConvTranspose2d(k4, s2, p1) IS the
 data-gradient of that geometry (TNR_DGRAD_4x4_S2) with its [in, out, 4, 4] weight read as a convolution weight [O = in, I = out], its
 input gradient is the forward kernel and its weight gradient the weight-gradient kernel with the roles of the two tensors swapped
-(engine.ConvOp on a shim module).  The 3-channel image sides are zero-extended to 4 channels (weights and buffers).  Layers of <= 4096
+(engine.ConvOp on a shim module).  upsample_mode "upconv" puts nn.Sequential(Upsample(nearest x2), Conv2d(k3, s1, p1)) where every
+ConvTranspose2d stands (block.upconv_block with act_type None); those layers run on csrc/conv_upconv_i2i.hip (engine.UpConvI2IOp), the
+encoder is unchanged.  The 3-channel image sides are zero-extended to 4 channels (weights and buffers).  Layers of <= 4096
 output pixels go through the im2col + split-K GEMM (the "im2col" row of ops.conv_plan), as in the discriminator's tail.
 """
 import torch
 import torch.nn as nn
 
 from .... import ops
-from ....engine import ConvOp, HipNet
+from ....engine import ConvOp, HipNet, UpConvI2IOp
 from ....ops import View, new_act
 from . import block as B
 from .ResNet_arch import ConvTranspose2dHIP
@@ -33,8 +35,8 @@ class UnetSkipConnectionBlock(nn.Module):
     def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False, norm="batch",
                  use_dropout=False, upsample_mode="deconv"):
         super().__init__()
-        if upsample_mode != "deconv":
-            raise NotImplementedError("HIP UnetGenerator implements the original deconv up-sampling")
+        if upsample_mode not in ("deconv", "upconv"):
+            raise NotImplementedError("HIP UnetGenerator implements the deconv and upconv up-sampling")
         self.outermost, self.innermost = outermost, innermost
         use_bias = norm == "instance"
         input_nc = outer_nc if input_nc is None else input_nc
@@ -43,14 +45,19 @@ class UnetSkipConnectionBlock(nn.Module):
         def norm_mod(nc):
             return B.BatchNorm2dHIP(nc, affine=True) if norm == "batch" else B.Marker("instancenorm")
 
+        def up_mod(in_nc, bias):
+            if upsample_mode == "deconv":
+                return ConvTranspose2dHIP(in_nc, outer_nc, 4, 2, bias=bias)
+            # block.upconv_block(act_type=None): Sequential(Upsample, Conv2d), the parameters under child 1
+            return nn.Sequential(B.Marker("upsample:nearest2"), B.Conv2dHIP(in_nc, outer_nc, 3, 1, bias=bias))
+
         if outermost:
-            model = [downconv, submodule, B.Marker("act:relu"), ConvTranspose2dHIP(inner_nc * 2, outer_nc, 4, 2, bias=True), B.Marker("tanh")]
+            model = [downconv, submodule, B.Marker("act:relu"), up_mod(inner_nc * 2, True), B.Marker("tanh")]
         elif innermost:
-            model = [B.Marker("act:leakyrelu"), downconv, B.Marker("act:relu"), ConvTranspose2dHIP(inner_nc, outer_nc, 4, 2, bias=use_bias),
-                     norm_mod(outer_nc)]
+            model = [B.Marker("act:leakyrelu"), downconv, B.Marker("act:relu"), up_mod(inner_nc, use_bias), norm_mod(outer_nc)]
         else:
             model = [B.Marker("act:leakyrelu"), downconv, norm_mod(inner_nc), submodule, B.Marker("act:relu"),
-                     ConvTranspose2dHIP(inner_nc * 2, outer_nc, 4, 2, bias=use_bias), norm_mod(outer_nc)]
+                     up_mod(inner_nc * 2, use_bias), norm_mod(outer_nc)]
             if use_dropout:
                 model.append(B.Marker("dropout0.5"))
         self.model = nn.Sequential(*model)
@@ -145,6 +152,11 @@ class _DConv:
             self.mod.weight.grad.add_(self.shim.weight.grad[:, :self.mod.weight.shape[1]])
 
 
+def _image_pad(uc):
+    """channels of the outermost decoder layer's NHWC output: the image zero-extended to a multiple of 4"""
+    return uc.opad if isinstance(uc, UpConvI2IOp) else uc.ipad
+
+
 class UnetGenerator(HipNet):
     def __init__(self, input_nc, output_nc, num_downs, ngf=64, norm_type="batch", use_dropout=False, upsample_mode="deconv"):
         super().__init__()
@@ -159,13 +171,14 @@ class UnetGenerator(HipNet):
         if num_downs < 5 or input_nc > 4 or output_nc > 4 or ngf % 8:
             raise NotImplementedError("HIP UnetGenerator needs num_downs >= 5, <= 4 image channels and ngf %% 8 == 0")
         self.input_nc, self.output_nc, self.num_downs, self.ngf, self.norm = input_nc, output_nc, num_downs, ngf, norm
-        blk = UnetSkipConnectionBlock(ngf * 8, ngf * 8, innermost=True, norm=norm)
+        um = dict(norm=norm, upsample_mode=upsample_mode)
+        blk = UnetSkipConnectionBlock(ngf * 8, ngf * 8, innermost=True, **um)
         for _ in range(num_downs - 5):
-            blk = UnetSkipConnectionBlock(ngf * 8, ngf * 8, submodule=blk, norm=norm, use_dropout=use_dropout)
-        blk = UnetSkipConnectionBlock(ngf * 4, ngf * 8, submodule=blk, norm=norm)
-        blk = UnetSkipConnectionBlock(ngf * 2, ngf * 4, submodule=blk, norm=norm)
-        blk = UnetSkipConnectionBlock(ngf, ngf * 2, submodule=blk, norm=norm)
-        self.model = UnetSkipConnectionBlock(output_nc, ngf, input_nc=input_nc, submodule=blk, outermost=True, norm=norm)
+            blk = UnetSkipConnectionBlock(ngf * 8, ngf * 8, submodule=blk, use_dropout=use_dropout, **um)
+        blk = UnetSkipConnectionBlock(ngf * 4, ngf * 8, submodule=blk, **um)
+        blk = UnetSkipConnectionBlock(ngf * 2, ngf * 4, submodule=blk, **um)
+        blk = UnetSkipConnectionBlock(ngf, ngf * 2, submodule=blk, **um)
+        self.model = UnetSkipConnectionBlock(output_nc, ngf, input_nc=input_nc, submodule=blk, outermost=True, **um)
         self._init_engine()
 
     # ------------------------------------------------------------------ executors
@@ -186,7 +199,9 @@ class UnetGenerator(HipNet):
         return out
 
     def _build_ops(self, packer):
-        self._lv = [(_DConv(dc, packer), dn, _TConv(uc, packer), un) for dc, dn, uc, un in self._levels()]
+        # (an up-conv level: the Sequential's Conv2d on the up-conv kernels, behind _TConv's interface)
+        up = lambda uc: UpConvI2IOp(uc[1]) if isinstance(uc, nn.Sequential) else _TConv(uc, packer)
+        self._lv = [(_DConv(dc, packer), dn, up(uc), un) for dc, dn, uc, un in self._levels()]
         self._ops = True
 
     def _refresh_derived(self):
@@ -256,7 +271,7 @@ class UnetGenerator(HipNet):
             ts[i], U[i - 1] = t, View(buf)
             src = U[i - 1]
         uc0 = lv[0][2]
-        o4 = View(new_act(N, H, W, uc0.ipad, dev))
+        o4 = View(new_act(N, H, W, _image_pad(uc0), dev))
         uc0.fwd(src, o4)                                  # (+ bias)
         pre = torch.empty((N, self.output_nc, H, W), dtype=torch.float32, device=dev)
         ops.nhwc_to_nchw(View(o4.buf, 0, self.output_nc), pre)
@@ -276,8 +291,8 @@ class UnetGenerator(HipNet):
         gpre = torch.empty_like(gout)
         ops.tanh_bwd(gout, out, gpre)
         uc0 = lv[0][2]
-        g4 = View(new_act(N, H, W, uc0.ipad, dev))
-        ops.nchw_to_nhwc(gpre, g4, Cpad=uc0.ipad)
+        g4 = View(new_act(N, H, W, _image_pad(uc0), dev))
+        ops.nchw_to_nhwc(gpre, g4, Cpad=g4.C)
         # ---- decoder, outermost inwards.  gU[i]: gradient of U[i] = [ReLU(a_i) | ReLU(d_{i+1})]
         if Wg:
             uc0.wgrad(g4, U[0])

@@ -896,6 +896,82 @@ def upconv3_wgrad(x, g, dw, db=None, alpha=1.0, beta=1.0):
         bias_grad(g, db, alpha=alpha, beta=beta)
 
 
+# ----------------------------------------------------------------------------------------------
+# nearest x2 + 3x3 of the image-to-image decoders (upsample_mode: upconv, Cin != Cout) as the transposed 4x4 stride-2 padding-1 convolution
+# of the LR tensor over the 16 folded taps (csrc/conv_upconv_i2i.hip).  ops.upconv_plan's four-tap launches stay the RRDBNet's: they were
+# built for its nf -> nf layers with an activation epilogue and take no part here.
+# ----------------------------------------------------------------------------------------------
+UPI2I_FAMILY = "conv_upconv_i2i"        # PROFILE family of the three launches, counted with the FLOP they execute (16 taps per LR pixel)
+
+
+class UpconvI2IWeights:
+    """The two fragment images of one layer's weight [Cout, Cin, 3, 3] in the arithmetic ops.MMA had when pack() last ran."""
+
+    def __init__(self, weight):
+        self.weight, self.mma, self.fwd, self.dgrad = weight, None, None, None
+
+    def pack(self):
+        lib, w = hip.load(), self.weight.detach()
+        Cout, Cin = w.shape[0], w.shape[1]
+        if tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous() or lib.tnr_upconv_i2i_pack_floats(Cout, Cin, 0, MMA) == 0:
+            raise hip.HipEngineError("upconv_i2i: a contiguous [Cout, Cin, 3, 3] weight, channels multiples of 4, Cout <= 512, Cin <= 2048 (got %s)"
+                                     % (tuple(w.shape),))
+        if self.mma != MMA or self.fwd is None:
+            self.fwd, self.dgrad = (torch.empty(lib.tnr_upconv_i2i_pack_floats(Cout, Cin, d, MMA), dtype=torch.float32, device=w.device)
+                                    for d in (0, 1))
+            self.mma = MMA
+        for d, img in ((0, self.fwd), (1, self.dgrad)):
+            hip.check(lib.tnr_upconv_i2i_pack(w.data_ptr(), Cout, Cin, d, MMA, img.data_ptr(), img.numel(), hip.stream()), "upconv_i2i_pack")
+
+    def image(self, dgrad):
+        if self.mma != MMA:                 # the process arithmetic changed since the last pack (tests switch it per case)
+            self.pack()
+        return self.dgrad if dgrad else self.fwd
+
+
+def _upi2i_check(who, wts, lo, hi):
+    Cout, Cin = wts.weight.shape[0], wts.weight.shape[1]
+    if (lo.C, hi.C) != (Cin, Cout) or (hi.N, hi.H, hi.W) != (lo.N, 2 * lo.H, 2 * lo.W):
+        raise hip.HipEngineError("%s: %s is not the x2 extent of %s over a %d -> %d layer" % (who, tuple(hi.buf.shape), tuple(lo.buf.shape), Cin, Cout))
+
+
+def upconv_i2i_fwd(x, wts, y, bias=None):
+    """y [N, 2H, 2W, Cout] = conv3x3(nearest_x2(x)) + bias in one launch over the LR view x (tnr_upconv_i2i_fwd).  Arithmetic: ops.MMA."""
+    _upi2i_check("upconv_i2i_fwd", wts, x, y)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(hip.load().tnr_upconv_i2i_fwd(x.c(), x.N, x.H, x.W, x.C, wts.image(False).data_ptr(), y.c(), y.C, hip.ptr(bias), MMA, hip.stream()),
+              "upconv_i2i_fwd")
+    if PROFILE is not None:
+        PROFILE.end(UPI2I_FAMILY, 2.0 * x.pixels * 16 * x.C * y.C, t0, (x.C, y.C, x.H, 0))
+
+
+def upconv_i2i_dgrad(g, wts, gx):
+    """gx [N, H, W, Cin] = the layer's data gradient in the LR domain from g [N, 2H, 2W, Cout] in one launch (tnr_upconv_i2i_dgrad)."""
+    _upi2i_check("upconv_i2i_dgrad", wts, gx, g)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(hip.load().tnr_upconv_i2i_dgrad(g.c(), gx.N, gx.H, gx.W, g.C, wts.image(True).data_ptr(), gx.c(), gx.C, MMA, hip.stream()),
+              "upconv_i2i_dgrad")
+    if PROFILE is not None:
+        PROFILE.end(UPI2I_FAMILY, 2.0 * gx.pixels * 16 * gx.C * g.C, t0, (gx.C, g.C, gx.H, 1))
+
+
+def upconv_i2i_wgrad(x, g, dw, db=None, alpha=1.0, beta=1.0):
+    """dw [Cout, Cin, 3, 3] = beta dw + alpha * the layer's weight gradient from the LR input x and g (tnr_upconv_i2i_wgrad: 16 folded-tap
+    products on the fp32 matrix core, then the 16 -> 9 unfold; deterministic); db likewise from tnr_bias_grad (may be None)."""
+    if (g.N, g.H, g.W) != (x.N, 2 * x.H, 2 * x.W) or tuple(dw.shape) != (g.C, x.C, 3, 3) or not dw.is_contiguous():
+        raise hip.HipEngineError("upconv_i2i_wgrad: g at twice the extent of x, dw [Cout, Cin, 3, 3]")
+    lib = hip.load()
+    need = lib.tnr_upconv_i2i_wgrad_workspace_bytes(x.N, x.H, x.W, x.C, g.C)
+    ws = WS.get("upconv_i2i_wgrad@%x" % hip.stream(), need, x.buf.device)
+    t0 = PROFILE.begin() if PROFILE is not None else None
+    hip.check(lib.tnr_upconv_i2i_wgrad(x.c(), g.c(), x.N, x.H, x.W, x.C, g.C, dw.data_ptr(), alpha, beta, ws.data_ptr(), ws.numel() * 8,
+                                       hip.stream()), "upconv_i2i_wgrad")
+    if PROFILE is not None:
+        PROFILE.end(UPI2I_FAMILY, 2.0 * x.pixels * 16 * x.C * g.C, t0, (x.C, g.C, x.H, 2))
+    if db is not None:
+        bias_grad(g, db, alpha=alpha, beta=beta)
+
+
 CHAIN_MAX = 6
 # The process switches of the dense-block forms (A/B switches: each turns ONE thing off or on).  Which form a block runs in is decided
 # by dense_block_plan below and nowhere else; DESIGN.md 3.2 has the table.
