@@ -58,34 +58,14 @@ static inline int tnr_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t tnr_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int tnr_round_up(int a, int b) { return tnr_cdiv(a, b) * b; }
 
-// Nearest x2 in front of a 3x3 s1 p1 convolution is the data-gradient of a virtual 4x4 s2 p1 convolution S whose 16 taps fold the 9
-// (DESIGN.md 3.12).  Per axis, folded tap k = 0..3 sums the 3x3 taps tnr_upfold_lo(k) .. tnr_upfold_hi(k): {2}, {1,2}, {0,1}, {0}.
-__host__ __device__ inline int tnr_upfold_lo(int k) { return k == 0 ? 2 : (k == 1 ? 1 : 0); }
-__host__ __device__ inline int tnr_upfold_hi(int k) { return k <= 1 ? 2 : (k == 2 ? 1 : 0); }
+// Nearest xS (S = 2 | 3) in front of a 3x3 s1 p1 convolution is a transposed (S + 2) x (S + 2) stride-S padding-1 convolution of the
+// low-resolution tensor whose T = S + 2 taps per axis fold the 3: LR pixel i reaches outputs S i - 1 + k, and folded tap
+// k = 0..T - 1 sums the 3x3 taps tnr_fold_lo(k) .. tnr_fold_hi(T, k) -- T = 4: {2}, {1,2}, {0,1}, {0}; T = 5: {2}, {1,2}, {0,1,2}, {0,1}, {0}.
+__host__ __device__ inline int tnr_fold_lo(int k) { return k >= 2 ? 0 : 2 - k; }
+__host__ __device__ inline int tnr_fold_hi(int T, int k) { return T - 1 - k < 2 ? T - 1 - k : 2; }
 // F[ky][kx] of the 3x3 filter w9, in ONE fp32 order: inside a row of the 3x3 filter over ascending kx first, then the row sums over ascending ky.
-__host__ __device__ inline float tnr_upfold_tap(const float *w9, int ky, int kx) {
-    const int ylo = tnr_upfold_lo(ky), yhi = tnr_upfold_hi(ky), xlo = tnr_upfold_lo(kx), xhi = tnr_upfold_hi(kx);
-    float r0 = w9[ylo * 3 + xlo];
-    if (xhi != xlo) r0 = r0 + w9[ylo * 3 + xhi];
-    if (yhi == ylo) return r0;
-    float r1 = w9[yhi * 3 + xlo];
-    if (xhi != xlo) r1 = r1 + w9[yhi * 3 + xhi];
-    return r0 + r1;
-}
-// The transpose: gradient of 3x3 tap (ty, tx) from the 16 gradients dF of the folded taps -- folded taps 2 - t and 3 - t per axis -- in
-// the same order: inside a row of dF over ascending kx first, then the two rows over ascending ky.
-__host__ __device__ inline float tnr_upfold_grad(const float *dF16, int ty, int tx) {
-    const int ky = 2 - ty, kx = 2 - tx;
-    return (dF16[ky * 4 + kx] + dF16[ky * 4 + kx + 1]) + (dF16[(ky + 1) * 4 + kx] + dF16[(ky + 1) * 4 + kx + 1]);
-}
-
-// Nearest x3 in front of a 3x3 s1 p1 convolution is the transposed 5x5 s3 p1 convolution of the low-resolution tensor: LR
-// pixel i reaches outputs 3i - 1 + k, and folded tap k = 0..4 sums the 3x3 taps tnr_up3fold_lo(k) .. tnr_up3fold_hi(k) per axis:
-// {2}, {1,2}, {0,1,2}, {0,1}, {0}.  Same fp32 order as tnr_upfold_tap: inside a row over ascending kx first, then the rows over ascending ky.
-__host__ __device__ inline int tnr_up3fold_lo(int k) { return k >= 2 ? 0 : 2 - k; }
-__host__ __device__ inline int tnr_up3fold_hi(int k) { return k <= 2 ? 2 : 4 - k; }
-__host__ __device__ inline float tnr_up3fold_tap(const float *w9, int ky, int kx) {
-    const int ylo = tnr_up3fold_lo(ky), yhi = tnr_up3fold_hi(ky), xlo = tnr_up3fold_lo(kx), xhi = tnr_up3fold_hi(kx);
+__host__ __device__ inline float tnr_fold_tap(const float *w9, int T, int ky, int kx) {
+    const int ylo = tnr_fold_lo(ky), yhi = tnr_fold_hi(T, ky), xlo = tnr_fold_lo(kx), xhi = tnr_fold_hi(T, kx);
     float sum = 0.f;
     for (int ty = ylo; ty <= yhi; ++ty) {
         float row = w9[ty * 3 + xlo];
@@ -94,7 +74,14 @@ __host__ __device__ inline float tnr_up3fold_tap(const float *w9, int ky, int kx
     }
     return sum;
 }
-// By output phase a = o mod 3 an output 3I + a reads tnr_up3_ntaps(a) LR neighbours per axis; neighbour t is LR pixel I + *d through
+// The transpose at T = 4: gradient of 3x3 tap (ty, tx) from the 16 gradients dF of the folded taps -- folded taps 2 - t and 3 - t per axis --
+// in the same order: inside a row of dF over ascending kx first, then the two rows over ascending ky.
+__host__ __device__ inline float tnr_upfold_grad(const float *dF16, int ty, int tx) {
+    const int ky = 2 - ty, kx = 2 - tx;
+    return (dF16[ky * 4 + kx] + dF16[ky * 4 + kx + 1]) + (dF16[(ky + 1) * 4 + kx] + dF16[(ky + 1) * 4 + kx + 1]);
+}
+
+// At S = 3, by output phase a = o mod 3 an output 3I + a reads tnr_up3_ntaps(a) LR neighbours per axis; neighbour t is LR pixel I + *d through
 // folded tap *k: a = 0: (I - 1, 4), (I, 1); a = 1: (I, 2); a = 2: (I, 3), (I + 1, 0).
 __host__ __device__ inline int tnr_up3_ntaps(int a) { return a == 1 ? 1 : 2; }
 __host__ __device__ inline void tnr_up3_phase_tap(int a, int t, int *d, int *k) {

@@ -5,21 +5,20 @@
 //             Wwin[co][dy s + i][dx s + j][c] = W[co][c s^2 + i s + j][dy][dx]   (zeros outside the image and for the pad channel c = 3)
 //   wgrad   : dWwin[wy][wx][c][co] = sum_{n, Y, X} img[n, (Y - 1) s + wy, (X - 1) s + wx, c] * g[n, Y, X, co], db = sum g
 // Both on the matrix cores with the window folded into the reduction (forward: K = (3s)^2 * 4 = 144 | 576) or into the rows
-// (weight gradient: M = 27 s^2 = 108 | 432, reduced over pixels).  A workgroup owns an 8 x 16 tile of output pixels and stages that
-// tile's image halo, ((T + 2) s)^2 pixels of 16 bytes, ONCE: a window row of 3s pixels is contiguous there, so a K step of the bf16
+// (weight gradient: M = 27 s^2 = 108 | 432, reduced over pixels).  A workgroup owns an 8 x 16 tile of output pixels (the forward on
+// mma_pixel.h's tile convention: the lane owns a pixel; its step reads the weights from LDS too and stays written here) and stages that tile's image halo, ((T + 2) s)^2 pixels of 16 bytes, ONCE: a window row of 3s pixels is contiguous there, so a K step of the bf16
 // matrix core (16 values = 4 pixels; a lane half takes 2 pixels = 8 values) is one 16-byte LDS read per plane.
-#include "conv_body.h"
+#include "mma_pixel.h"
 
 namespace {
 
-constexpr int UT_H = 8, UT_W = 16;            // output pixels per workgroup: 4 waves x (2 rows x 16 columns = one 32-pixel MFMA block)
 constexpr int UW_GRID = 256;                  // weight gradient: persistent workgroups (= partial slabs), one per CU
 
 template <int S> struct UGeom {
     static constexpr int WS = 3 * S;                          // window side in image pixels
     static constexpr int K = WS * WS * 4;                     // forward reduction: (wy, wx, 4 channels)
     static constexpr int KSTEPS = K / 16;                     // 9 | 36
-    static constexpr int TH = (UT_H + 2) * S, TW = (UT_W + 2) * S, NPIX = TH * TW;      // staged image halo
+    static constexpr int TH = (MP_TH + 2) * S, TW = (MP_TW + 2) * S, NPIX = TH * TW;      // staged image halo
     static constexpr int M = WS * WS * 3;                     // weight-gradient rows: (wy, wx, 3 channels); row M = the bias sum
     static constexpr int NMT = (M + 1 + 31) / 32;             // 32-row blocks: 4 | 14
 };
@@ -36,7 +35,7 @@ struct UnshufK {
 };
 
 template <int S, int NT, int MMA> constexpr int unshuffle_fwd_lds() {
-    constexpr int np = MMA == TNR_MMA_BF16X3 ? 3 : 1;
+    constexpr int np = mp_planes(MMA);
     constexpr int img = MMA == TNR_MMA_F32 ? UGeom<S>::NPIX * 16 : UGeom<S>::NPIX * 8 * np;
     constexpr int units = MMA == TNR_MMA_F32 ? UF_CHUNK * 2 * 2 : UF_CHUNK * np * 2;      // 16-byte units per output channel
     return img + units * NT * 32 * 16;
@@ -65,7 +64,7 @@ __global__ void __launch_bounds__(256) conv_unshuffle_kernel(const UnshufK a) {
     bid /= a.tiles_x;
     const int ty = bid % a.tiles_y;
     const int n = bid / a.tiles_y;
-    const int y0 = ty * UT_H, x0 = tx * UT_W;
+    const int y0 = ty * MP_TH, x0 = tx * MP_TW;
 
     // ---- weights: item = (8-value group gi of the chunk, cout j) = 2 float4
     constexpr int ITEMS = UF_CHUNK * 2 * NF, R = (ITEMS + 255) / 256;
@@ -103,7 +102,7 @@ __global__ void __launch_bounds__(256) conv_unshuffle_kernel(const UnshufK a) {
     };
     load_w(0);
 
-    // ---- the image halo, once: rows (y0 - 1) s .. (y0 + UT_H + 1) s - 1, zeros outside the image (= the layer's zero padding)
+    // ---- the image halo, once: rows (y0 - 1) s .. (y0 + MP_TH + 1) s - 1, zeros outside the image (= the layer's zero padding)
     {
         const int iy0 = (y0 - 1) * S, ix0 = (x0 - 1) * S;
         for (int p = tid; p < G::NPIX; p += 256) {
@@ -218,7 +217,7 @@ struct UWgradK {
     int tiles_x, tiles_y, tiles;
 };
 
-template <int S, int NT> constexpr int unshuffle_wgrad_lds() { return UGeom<S>::NPIX * 16 + UT_H * UT_W * NT * 32 * 4; }
+template <int S, int NT> constexpr int unshuffle_wgrad_lds() { return UGeom<S>::NPIX * 16 + MP_TH * MP_TW * NT * 32 * 4; }
 
 // D[m][co] += A[m][pixel] B[pixel][co] with v_mfma_f32_32x32x2_f32 (fp32 products, fp32 accumulate): m = (wy (3s) + wx) 3 + c is
 // a row of the window, A[m][pixel] = the halo value at the pixel's window origin + (wy, wx), channel c -- one 4-byte LDS read per
@@ -261,7 +260,7 @@ __global__ void __launch_bounds__(256) wgrad_unshuffle_kernel(const UWgradK a) {
         q /= a.tiles_x;
         const int ty = q % a.tiles_y;
         const int n = q / a.tiles_y;
-        const int y0 = ty * UT_H, x0 = tx * UT_W;
+        const int y0 = ty * MP_TH, x0 = tx * MP_TW;
         __syncthreads();
         const int iy0 = (y0 - 1) * S, ix0 = (x0 - 1) * S;
         for (int p = tid; p < G::NPIX; p += 256) {
@@ -271,23 +270,23 @@ __global__ void __launch_bounds__(256) wgrad_unshuffle_kernel(const UWgradK a) {
             if (Y >= 0 && Y < a.H && X >= 0 && X < a.W) v = *reinterpret_cast<const f32x4 *>(a.x + (((size_t)n * a.H + Y) * a.W + X) * 4);
             *reinterpret_cast<f32x4 *>(s_img + p * 4) = v;
         }
-        for (int i = tid; i < UT_H * UT_W * (NF / 4); i += 256) {      // g of the tile; zeros beyond the output grid
+        for (int i = tid; i < MP_TH * MP_TW * (NF / 4); i += 256) {      // g of the tile; zeros beyond the output grid
             const int pix = i / (NF / 4), c4 = i - pix * (NF / 4);
-            const int oy = y0 + pix / UT_W, ox = x0 + pix % UT_W;
+            const int oy = y0 + pix / MP_TW, ox = x0 + pix % MP_TW;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (oy < a.Ho && ox < a.Wo) v = *reinterpret_cast<const f32x4 *>(a.g + (((size_t)n * a.Ho + oy) * a.Wo + ox) * a.g_ct + a.g_co + c4 * 4);
             *reinterpret_cast<f32x4 *>(s_g + pix * NF + c4 * 4) = v;
         }
         __syncthreads();
 #pragma unroll 1
-        for (int ly = 0; ly < UT_H; ++ly) {
+        for (int ly = 0; ly < MP_TH; ++ly) {
 #pragma unroll
-            for (int kx = 0; kx < UT_W / 2; ++kx) {
+            for (int kx = 0; kx < MP_TW / 2; ++kx) {
                 const int lx = 2 * kx + half;                               // this lane half's pixel of the K step
                 const int pixoff = (ly * S * G::TW + lx * S) * 4;
                 float bv[NT];
 #pragma unroll
-                for (int nn = 0; nn < NT; ++nn) bv[nn] = s_g[(ly * UT_W + lx) * NF + nn * 32 + li];
+                for (int nn = 0; nn < NT; ++nn) bv[nn] = s_g[(ly * MP_TW + lx) * NF + nn * 32 + li];
 #pragma unroll
                 for (int t = 0; t < MTW; ++t) {
                     if (wave + 4 * t < G::NMT) {                           // wave-uniform
@@ -358,11 +357,7 @@ int unshuffle_geometry(const char *who, tnr_view x, int N, int H, int W, int nf,
     TNR_REQUIRE(s == 2 || s == 4, "%s: unshuffle scale must be 2 or 4 (got %d)", who, s);
     TNR_REQUIRE(H % s == 0 && W % s == 0, "%s: image %d x %d is no multiple of the unshuffle scale %d", who, H, W, s);
     TNR_REQUIRE(nf == 32 || nf == 64, "%s: nf must be 32 or 64 (got %d)", who, nf);
-    *tiles_x = tnr_cdiv(W / s, UT_W);
-    *tiles_y = tnr_cdiv(H / s, UT_H);
-    *tiles = (int64_t)*tiles_x * *tiles_y * N;
-    TNR_REQUIRE(*tiles < (1LL << 31), "%s: grid too large", who);
-    return TNR_OK;
+    return mp_geometry(who, N, H / s, W / s, 1, tiles_x, tiles_y, tiles);
 }
 
 }  // namespace
@@ -371,30 +366,23 @@ extern "C" int tnr_conv_unshuffle_fwd(tnr_view x, int32_t N, int32_t H, int32_t 
                                       const float *bias, int32_t mma, void *stream) {
     UnshufK k;
     int64_t tiles;
-    int rc = unshuffle_geometry("conv_unshuffle_fwd", x, N, H, W, nf, s, &k.tiles_x, &k.tiles_y, &tiles);
+    const int rc = unshuffle_geometry("conv_unshuffle_fwd", x, N, H, W, nf, s, &k.tiles_x, &k.tiles_y, &tiles);
     if (rc != TNR_OK) return rc;
     TNR_REQUIRE(wp && y.ptr && (y.ctot % 4) == 0 && (y.coff % 4) == 0 && y.coff + nf <= y.ctot, "conv_unshuffle_fwd: bad output view");
-    TNR_REQUIRE(mma == TNR_MMA_F32 || mma == TNR_MMA_BF16 || mma == TNR_MMA_BF16X3, "conv_unshuffle_fwd: bad mma %d", mma);
+    TNR_REQUIRE(mp_mma_ok(mma), "conv_unshuffle_fwd: bad mma %d", mma);
     k.x = x.ptr; k.N = N; k.H = H; k.W = W; k.wp = wp;
     k.y = y.ptr; k.y_ct = y.ctot; k.y_co = y.coff; k.Ho = H / s; k.Wo = W / s;
     k.bias = bias;
     static int cus = 0;
 #define U_FWD(S, NT, MMA) tnr_kernel_lds(conv_unshuffle_kernel<S, NT, MMA>, unshuffle_fwd_lds<S, NT, MMA>())
-#define U_FWD_MODES(S, NT) U_FWD(S, NT, TNR_MMA_F32), U_FWD(S, NT, TNR_MMA_BF16), U_FWD(S, NT, TNR_MMA_BF16X3)
-    rc = tnr_kernel_setup(&cus, "conv_unshuffle_fwd", {U_FWD_MODES(2, 1), U_FWD_MODES(2, 2), U_FWD_MODES(4, 1), U_FWD_MODES(4, 2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[12] = {U_FWD_MODES(2, 1), U_FWD_MODES(2, 2), U_FWD_MODES(4, 1), U_FWD_MODES(4, 2)};
-#undef U_FWD_MODES
+    return mp_launch(&cus, "conv_unshuffle_fwd", {MP_MODES(U_FWD, 2, 1), MP_MODES(U_FWD, 2, 2), MP_MODES(U_FWD, 4, 1), MP_MODES(U_FWD, 4, 2)},
+                     ((s == 4 ? 2 : 0) + (nf == 64 ? 1 : 0)) * 3 + mma, dim3((unsigned)tiles), &k, stream);
 #undef U_FWD
-    const tnr_kernel_lds &kl = table[((s == 4 ? 2 : 0) + (nf == 64 ? 1 : 0)) * 3 + mma];      // (TNR_MMA_F32, _BF16, _BF16X3 = 0, 1, 2)
-    void *args[] = {&k};
-    (void)hipLaunchKernel(kl.fn, dim3((unsigned)tiles), dim3(256), args, kl.lds, (hipStream_t)stream);
-    return tnr_check_launch("conv_unshuffle_fwd");
 }
 
 extern "C" int64_t tnr_wgrad_unshuffle_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t nf, int32_t s) {
     if (s != 2 && s != 4) return 0;
-    const int64_t tiles = (int64_t)tnr_cdiv(W / s, UT_W) * tnr_cdiv(H / s, UT_H) * N;
+    const int64_t tiles = mp_tiles(N, H / s, W / s);
     return (int64_t)unshuffle_wgrad_grid(tiles) * (27 * s * s + 1) * nf * (int64_t)sizeof(float);
 }
 
@@ -412,19 +400,12 @@ extern "C" int tnr_wgrad_unshuffle(tnr_view g, tnr_view x, int32_t N, int32_t H,
     const int grid = unshuffle_wgrad_grid(tiles);
     static int cus = 0;
 #define U_WG(S, NT) tnr_kernel_lds(wgrad_unshuffle_kernel<S, NT>, unshuffle_wgrad_lds<S, NT>())
-    rc = tnr_kernel_setup(&cus, "wgrad_unshuffle", {U_WG(2, 1), U_WG(2, 2), U_WG(4, 1), U_WG(4, 2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[4] = {U_WG(2, 1), U_WG(2, 2), U_WG(4, 1), U_WG(4, 2)};
+    rc = mp_launch(&cus, "wgrad_unshuffle", {U_WG(2, 1), U_WG(2, 2), U_WG(4, 1), U_WG(4, 2)}, (s == 4 ? 2 : 0) + (nf == 64 ? 1 : 0), dim3(grid), &k, stream);
 #undef U_WG
-    const tnr_kernel_lds &kl = table[(s == 4 ? 2 : 0) + (nf == 64 ? 1 : 0)];
-    void *args[] = {&k};
-    hipStream_t st = (hipStream_t)stream;
-    (void)hipLaunchKernel(kl.fn, dim3(grid), dim3(256), args, kl.lds, st);
-    rc = tnr_check_launch("wgrad_unshuffle");
     if (rc != TNR_OK) return rc;
     UWgradRedK r;
     r.ws = ws; r.grid = grid; r.nf = nf; r.s = s;
     r.dw = dw; r.db = db; r.alpha = alpha; r.beta = beta;
-    hipLaunchKernelGGL(wgrad_unshuffle_reduce_kernel, dim3(tnr_cdiv((27 * s * s + 1) * nf, 256)), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(wgrad_unshuffle_reduce_kernel, dim3(tnr_cdiv((27 * s * s + 1) * nf, 256)), dim3(256), 0, (hipStream_t)stream, r);
     return tnr_check_launch("wgrad_unshuffle_reduce");
 }

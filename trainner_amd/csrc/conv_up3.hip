@@ -1,35 +1,29 @@
 // RRDBNet's x3 up-conv layer (upscale 3: nearest x3, then a 3x3 pad-1 convolution nf -> nf, then LeakyReLU) as the transposed 5x5 stride-3
 // padding-1 convolution of the LOW-resolution tensor it is exactly, borders included.  LR pixel i reaches the HR outputs
-// 3i - 1 + k through folded tap k = 0..4 (common.h tnr_up3fold_*); by output phase (o mod 3) an output reads the LR neighbours
+// 3i - 1 + k through folded tap k = 0..4 (common.h tnr_fold_*, 5 taps); by output phase (o mod 3) an output reads the LR neighbours
 // {i - 1, i}, {i}, {i, i + 1} per axis: 4 + 2 + 4 + 2 + 1 + 2 + 4 + 2 + 4 = 25 products per LR pixel and channel pair against the 81 of the
 // layer written out in the HR domain.  The up-sampled tensor never exists, in any of the three passes.
 //   forward : y[3I + a, 3J + b] = act(bias + sum over the phase's taps of K[ky][kx] x[I + dy, J + dx])             nine GEMMs per LR tile
 //   dgrad   : gx[i, j] = sum_k K[ky][kx]^T g[3i - 1 + ky, 3j - 1 + kx]  (* LeakyReLU'(mask))                        K = 25 nf
 //   wgrad   : dK[ky][kx][ci][co] = sum over LR pixels x[I + dy, J + dx, ci] g[3I + a, 3J + b, co], then the 25 -> 9 unfold
-// Forward and data gradient: a workgroup (4 waves) owns an 8 x 16 LR tile; wave w owns tile rows 2w, 2w + 1 = one 32-pixel block of the
-// matrix core's B operand and all nf produced channels (A = the folded weights, so a lane ends up holding 4 consecutive channels of ITS
-// pixel: the store is a float4 per lane).  The activations are staged in LDS once (forward: the tile + a one-pixel zero halo; data gradient:
+// Forward and data gradient on mma_pixel.h's tile convention (an 8 x 16 LR tile per workgroup, the lane owns a pixel), every workgroup with
+// all nf produced channels.  The activations are staged in LDS once (forward: the tile + a one-pixel zero halo; data gradient:
 // the (3 * 8 + 2) x (3 * 16 + 2) gradient window in chunks of 16 channels) in the operand format of the arithmetic -- fp32, bf16, or the exact
 // hi / mid / lo bf16 planes.  The folded weights do not fit LDS (25 x 64 x 64: 410 KB in fp32); TNR_PACK_UP3_* lays them out as ready A
 // fragments in consumption order (already split for TNR_MMA_BF16X3, already rounded for TNR_MMA_BF16), so a wave streams them from L2 with one
 // coalesced 16-byte load per lane and fragment, one step (a tap x 16 reduced channels) ahead of the matrix core; the main loop has no barrier.
-#include "conv_epilogue.h"
+// Sums: a tap's (forward) | a tap row's (data gradient) steps grow in one accumulation chain, then added to the running sum.
+#include "mma_pixel.h"
 
 namespace {
 
-constexpr int U3_TH = 8, U3_TW = 16;                       // LR pixels per workgroup
-constexpr int U3_FH = U3_TH + 2, U3_FW = U3_TW + 2;        // forward: the staged tile with its halo, 180 pixels
-constexpr int U3_GH = 3 * U3_TH + 2, U3_GW = 3 * U3_TW + 2; // data gradient: the staged window of g, 26 x 50 = 1300 pixels
+constexpr int U3_FH = MP_TH + 2, U3_FW = MP_TW + 2;        // forward: the staged tile with its halo, 180 pixels
+constexpr int U3_GH = 3 * MP_TH + 2, U3_GW = 3 * MP_TW + 2; // data gradient: the staged window of g, 26 x 50 = 1300 pixels
 constexpr int U3_WG_SLABS = 20;                            // weight gradient: pixel-block slabs per folded tap (25 x 20 workgroups)
-
-template <int NT, int MMA> struct U3Frag {                 // one step's A fragments of a lane: all NT 32-row blocks
-    f32x4 f[MMA == TNR_MMA_F32 ? 2 : 1][NT];
-    tnr_bf16x8 b[MMA == TNR_MMA_BF16X3 ? 3 : 1][NT];
-};
 
 // fragments of step s from the packed image (pack_api.hip: fp32 region [s][8-group][half][row][4], then bf16 region [s][plane][half][row][8 bf16])
 template <int NT, int MMA>
-__device__ __forceinline__ void u3_load_w(U3Frag<NT, MMA> &w, const float *wp, const int s, const int li, const int half) {
+__device__ __forceinline__ void u3_load_w(MpFrag<NT, MMA> &w, const float *wp, const int s, const int li, const int half) {
     constexpr int NF = NT * 32, KS = NF / 16;
     if constexpr (MMA == TNR_MMA_F32) {
         const float *base = wp + (size_t)s * 16 * NF;
@@ -38,74 +32,12 @@ __device__ __forceinline__ void u3_load_w(U3Frag<NT, MMA> &w, const float *wp, c
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) w.f[g][nn] = *reinterpret_cast<const f32x4 *>(base + ((g * 2 + half) * NF + nn * 32 + li) * 4);
     } else {
-        constexpr int NP = MMA == TNR_MMA_BF16X3 ? 3 : 1;
         const float *base = wp + (size_t)25 * KS * NF * 16 + (size_t)s * 24 * NF;
 #pragma unroll
-        for (int p = 0; p < NP; ++p)
+        for (int p = 0; p < mp_planes(MMA); ++p)
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) w.b[p][nn] = *reinterpret_cast<const tnr_bf16x8 *>(base + ((p * 2 + half) * NF + nn * 32 + li) * 4);
     }
-}
-
-// part += A (this step's weights) x B (16 channels of the lane's pixel, read from LDS at `pf` (fp32) | `pb` + plane * plane_stride (bf16))
-template <int NT, int MMA>
-__device__ __forceinline__ void u3_step(f32x16 (&part)[NT], const U3Frag<NT, MMA> &w, const float *pf, const __bf16 *pb, const int plane_stride,
-                                        const int half) {
-    if constexpr (MMA == TNR_MMA_F32) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const f32x4 av = *reinterpret_cast<const f32x4 *>(pf + g * 8 + half * 4);
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int nn = 0; nn < NT; ++nn) part[nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.f[g][nn][m], av[m], part[nn], 0, 0, 0);
-        }
-    } else {
-        constexpr int NP = MMA == TNR_MMA_BF16X3 ? 3 : 1;
-        tnr_bf16x8 ca[NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) ca[p] = *reinterpret_cast<const tnr_bf16x8 *>(pb + p * plane_stride + half * 8);
-        if constexpr (NP == 3) {
-            // the six kept partial products, smallest first (as in conv_body.h)
-            constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int nn = 0; nn < NT; ++nn) part[nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.b[TB[q]][nn], ca[TA[q]], part[nn], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int nn = 0; nn < NT; ++nn) part[nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.b[0][nn], ca[0], part[nn], 0, 0, 0);
-        }
-    }
-}
-
-// four channels of a staged pixel into LDS in the operand format: fp32, or NP bf16 planes (exact split; one plane = the rounding)
-template <int MMA>
-__device__ __forceinline__ void u3_stage4(f32x4 v, float *sf, __bf16 *sb, const int plane_stride) {
-    if constexpr (MMA == TNR_MMA_F32) {
-        *reinterpret_cast<f32x4 *>(sf) = v;
-    } else {
-        constexpr int NP = MMA == TNR_MMA_BF16X3 ? 3 : 1;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            tnr_bf16x4 pk;
-            f32x4 res;
-            tnr_pk_level(v, pk, res);
-            *reinterpret_cast<tnr_bf16x4 *>(sb + p * plane_stride) = pk;
-            v = res;
-        }
-    }
-}
-
-template <int NT> __device__ __forceinline__ void u3_zero(f32x16 (&v)[NT]) {
-#pragma unroll
-    for (int nn = 0; nn < NT; ++nn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[nn][r] = 0.f;
-}
-template <int NT> __device__ __forceinline__ void u3_add(f32x16 (&acc)[NT], const f32x16 (&part)[NT]) {
-#pragma unroll
-    for (int nn = 0; nn < NT; ++nn) acc[nn] += part[nn];
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -120,7 +52,7 @@ struct Up3FwdK {
 // LDS pixel stride: nf + 4 floats | nf + 8 bf16, an odd number of 16-byte units, so the 16-byte reads of 8 consecutive pixels meet 8 bank groups
 template <int NT, int MMA> constexpr int up3_fwd_lds() {
     constexpr int NF = NT * 32, px = U3_FH * U3_FW;
-    return MMA == TNR_MMA_F32 ? px * (NF + 4) * 4 : px * (NF + 8) * 2 * (MMA == TNR_MMA_BF16X3 ? 3 : 1);
+    return MMA == TNR_MMA_F32 ? px * (NF + 4) * 4 : px * (NF + 8) * 2 * mp_planes(MMA);
 }
 
 template <int NT, int MMA>
@@ -137,9 +69,10 @@ __global__ void __launch_bounds__(256) up3_fwd_kernel(const Up3FwdK a) {
     bid /= a.tiles_x;
     const int ty = bid % a.tiles_y;
     const int n = bid / a.tiles_y;
-    const int y0 = ty * U3_TH, x0 = tx * U3_TW;
+    const int y0 = ty * MP_TH, x0 = tx * MP_TW;
+    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // mma_pixel.h: the lane's pixel of the tile
 
-    U3Frag<NT, MMA> cur, nxt;
+    MpFrag<NT, MMA> cur, nxt;
     u3_load_w<NT, MMA>(cur, a.wp, 0, li, half);
     nxt = cur;
 
@@ -150,19 +83,18 @@ __global__ void __launch_bounds__(256) up3_fwd_kernel(const Up3FwdK a) {
         const int Y = y0 - 1 + r, X = x0 - 1 + c;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (Y >= 0 && Y < a.H && X >= 0 && X < a.W) v = *reinterpret_cast<const f32x4 *>(a.x + (((size_t)n * a.H + Y) * a.W + X) * a.x_ct + a.x_co + c4 * 4);
-        u3_stage4<MMA>(v, s_f + p * PSF + c4 * 4, s_b + p * PSB + c4 * 4, PLANE);
+        mp_stage4<MMA>(v, s_f + p * PSF + c4 * 4, s_b + p * PSB + c4 * 4, PLANE);
     }
     __syncthreads();
 
-    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // this lane's LR pixel (the B operand's column)
-    const int abase = (ly + 1) * U3_FW + lx + 1;
+    const int abase = (ly + 1) * U3_FW + lx + 1;                    // the lane's LR pixel in the staged tile
     const bool inside = y0 + ly < a.H && x0 + lx < a.W;
     int s = 0;
 #pragma unroll 1
     for (int ph = 0; ph < 9; ++ph) {
         const int pa = ph / 3, pb = ph - pa * 3;
         f32x16 acc[NT];
-        u3_zero<NT>(acc);
+        mp_zero<NT>(acc);
 #pragma unroll 1
         for (int t = 0; t < tnr_up3_ntaps(pa) * tnr_up3_ntaps(pb); ++t) {
             int dy, dx, ky, kx;
@@ -170,16 +102,16 @@ __global__ void __launch_bounds__(256) up3_fwd_kernel(const Up3FwdK a) {
             tnr_up3_phase_tap(pb, t % tnr_up3_ntaps(pb), &dx, &kx);
             const int pix = abase + dy * U3_FW + dx;
             f32x16 part[NT];                                        // one tap's nf products, then added to the phase's sum
-            u3_zero<NT>(part);
+            mp_zero<NT>(part);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks, ++s) {
                 if (s + 1 < 25 * KS) u3_load_w<NT, MMA>(nxt, a.wp, s + 1, li, half);
-                u3_step<NT, MMA>(part, cur, s_f + pix * PSF + ks * 16, s_b + pix * PSB + ks * 16, PLANE, half);
+                mp_step<NT, MMA>(part, cur, s_f + pix * PSF + ks * 16, s_b + pix * PSB + ks * 16, PLANE, half);
                 cur = nxt;
             }
-            u3_add<NT>(acc, part);
+            mp_add<NT>(acc, part);
         }
-        // ---- this phase's pixel (3 (y0 + ly) + pa, 3 (x0 + lx) + pb): the lane holds channels 8 q + 4 half .. + 3 of every 32-block
+        // ---- this phase's pixel (3 (y0 + ly) + pa, 3 (x0 + lx) + pb)
         if (inside) {
             float *yp = a.y + (((size_t)n * 3 * a.H + 3 * (y0 + ly) + pa) * 3 * a.W + 3 * (x0 + lx) + pb) * a.y_ct + a.y_co;
 #pragma unroll
@@ -208,7 +140,7 @@ struct Up3DgradK {
 // one 16-channel chunk of the window: 64 bytes per pixel in fp32, 32 bytes per pixel and plane in the bf16 forms (83 KB | 42 KB | 125 KB)
 template <int MMA> constexpr int up3_dgrad_lds() {
     constexpr int px = U3_GH * U3_GW;
-    return MMA == TNR_MMA_F32 ? px * 64 : px * 32 * (MMA == TNR_MMA_BF16X3 ? 3 : 1);
+    return MMA == TNR_MMA_F32 ? px * 64 : px * 32 * mp_planes(MMA);
 }
 
 template <int NT, int MMA>
@@ -224,17 +156,17 @@ __global__ void __launch_bounds__(256) up3_dgrad_kernel(const Up3DgradK a) {
     bid /= a.tiles_x;
     const int ty = bid % a.tiles_y;
     const int n = bid / a.tiles_y;
-    const int y0 = ty * U3_TH, x0 = tx * U3_TW;
+    const int y0 = ty * MP_TH, x0 = tx * MP_TW;
+    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // mma_pixel.h: the lane's pixel of the tile
     const int Hh = 3 * a.H, Wh = 3 * a.W;
 
-    U3Frag<NT, MMA> cur, nxt;
+    MpFrag<NT, MMA> cur, nxt;
     u3_load_w<NT, MMA>(cur, a.wp, 0, li, half);
     nxt = cur;
 
-    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // this lane's LR pixel; its window starts at (3 ly, 3 lx)
-    const int abase = 3 * ly * U3_GW + 3 * lx;
+    const int abase = 3 * ly * U3_GW + 3 * lx;                      // the lane's LR pixel: its window starts at (3 ly, 3 lx)
     f32x16 acc[NT];
-    u3_zero<NT>(acc);
+    mp_zero<NT>(acc);
     int s = 0;
 #pragma unroll 1
     for (int ks = 0; ks < KS; ++ks) {
@@ -247,21 +179,21 @@ __global__ void __launch_bounds__(256) up3_dgrad_kernel(const Up3DgradK a) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (Y >= 0 && Y < Hh && X >= 0 && X < Wh)
                 v = *reinterpret_cast<const f32x4 *>(a.g + (((size_t)n * Hh + Y) * Wh + X) * a.g_ct + a.g_co + ks * 16 + c4 * 4);
-            u3_stage4<MMA>(v, s_f + p * 16 + c4 * 4, s_b + p * 16 + c4 * 4, PLANE);
+            mp_stage4<MMA>(v, s_f + p * 16 + c4 * 4, s_b + p * 16 + c4 * 4, PLANE);
         }
         __syncthreads();
 #pragma unroll 1
         for (int ky = 0; ky < 5; ++ky) {
             f32x16 part[NT];                                        // one row of taps (80 products), then added to the running sum
-            u3_zero<NT>(part);
+            mp_zero<NT>(part);
 #pragma unroll
             for (int kx = 0; kx < 5; ++kx, ++s) {
                 if (s + 1 < 25 * KS) u3_load_w<NT, MMA>(nxt, a.wp, s + 1, li, half);
                 const int pix = abase + ky * U3_GW + kx;
-                u3_step<NT, MMA>(part, cur, s_f + pix * 16, s_b + pix * 16, PLANE, half);
+                mp_step<NT, MMA>(part, cur, s_f + pix * 16, s_b + pix * 16, PLANE, half);
                 cur = nxt;
             }
-            u3_add<NT>(acc, part);
+            mp_add<NT>(acc, part);
         }
     }
     if (y0 + ly < a.H && x0 + lx < a.W) {
@@ -291,7 +223,7 @@ struct Up3WgradK {
     int tiles_x, tiles_y, tiles, slabs;
 };
 
-template <int NT> constexpr int up3_wgrad_lds() { return 2 * U3_TH * U3_TW * NT * 32 * 4; }
+template <int NT> constexpr int up3_wgrad_lds() { return 2 * MP_TPIX * NT * 32 * 4; }
 
 // Workgroup (tap k = ky * 5 + kx, slab): dK[k] over the tiles slab, slab + slabs, ...  Per tile it stages the tap's two operands -- x of the
 // tile shifted by the tap's LR offset (zeros outside the image) and g at the tap's phase of the tile's 3 x 3 blocks -- and every wave
@@ -299,7 +231,7 @@ template <int NT> constexpr int up3_wgrad_lds() { return 2 * U3_TH * U3_TW * NT 
 // workgroup's tiles.  The four waves' sums are then added in wave order through LDS: the order in which every partial sum grows is fixed.
 template <int NT>
 __global__ void __launch_bounds__(256) up3_wgrad_kernel(const Up3WgradK a) {
-    constexpr int NF = NT * 32, TPIX = U3_TH * U3_TW;
+    constexpr int NF = NT * 32, TPIX = MP_TPIX;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *s_x = reinterpret_cast<float *>(smem);
     float *s_g = s_x + TPIX * NF;
@@ -313,7 +245,7 @@ __global__ void __launch_bounds__(256) up3_wgrad_kernel(const Up3WgradK a) {
 
     f32x16 acc[NT][NT];
 #pragma unroll
-    for (int ib = 0; ib < NT; ++ib) u3_zero<NT>(acc[ib]);
+    for (int ib = 0; ib < NT; ++ib) mp_zero<NT>(acc[ib]);
 
     for (int tile = blockIdx.y; tile < a.tiles; tile += a.slabs) {
         int q = tile;
@@ -321,11 +253,11 @@ __global__ void __launch_bounds__(256) up3_wgrad_kernel(const Up3WgradK a) {
         q /= a.tiles_x;
         const int ty = q % a.tiles_y;
         const int n = q / a.tiles_y;
-        const int y0 = ty * U3_TH, x0 = tx * U3_TW;
+        const int y0 = ty * MP_TH, x0 = tx * MP_TW;
         __syncthreads();
         for (int i = tid; i < TPIX * (NF / 4); i += 256) {
             const int p = i / (NF / 4), c4 = i - p * (NF / 4);
-            const int I = y0 + p / U3_TW, J = x0 + p % U3_TW;
+            const int I = y0 + p / MP_TW, J = x0 + p % MP_TW;
             f32x4 xv = {0.f, 0.f, 0.f, 0.f}, gv = {0.f, 0.f, 0.f, 0.f};
             if (I < a.H && J < a.W) {
                 gv = *reinterpret_cast<const f32x4 *>(a.g + (((size_t)n * Hh + 3 * I + pa) * Wh + 3 * J + pb) * a.g_ct + a.g_co + c4 * 4);
@@ -391,75 +323,56 @@ __global__ void __launch_bounds__(256) up3_wgrad_unfold_kernel(const Up3UnfoldK 
     a.dw[o] = (a.beta != 0.f ? a.beta * a.dw[o] : 0.f) + a.alpha * sum;
 }
 
+// ------------------------------------------------------------------------------------------------ host side
 int up3_geometry(const char *who, int N, int H, int W, int nf, int *tiles_x, int *tiles_y, int64_t *tiles) {
-    TNR_REQUIRE(N > 0 && H > 0 && W > 0, "%s: bad arguments", who);
+    const int rc = mp_geometry(who, N, H, W, 3, tiles_x, tiles_y, tiles);
+    if (rc != TNR_OK) return rc;
     TNR_REQUIRE(nf == 32 || nf == 64, "%s: nf must be 32 or 64 (got %d)", who, nf);
-    TNR_REQUIRE((int64_t)3 * H < (1 << 30) && (int64_t)3 * W < (1 << 30), "%s: image too large", who);
-    *tiles_x = tnr_cdiv(W, U3_TW);
-    *tiles_y = tnr_cdiv(H, U3_TH);
-    *tiles = (int64_t)*tiles_x * *tiles_y * N;
-    TNR_REQUIRE(*tiles < (1LL << 31), "%s: grid too large", who);
     return TNR_OK;
 }
 
-bool up3_view_ok(const tnr_view &v, int nf) { return v.ptr != nullptr && view_aligned(v) && v.coff >= 0 && v.coff + nf <= v.ctot; }
 int up3_wgrad_slabs(int64_t tiles) { return tiles < U3_WG_SLABS ? (int)tiles : U3_WG_SLABS; }
 
 }  // namespace
-
-#define U3_MODES(K, NT) K(NT, TNR_MMA_F32), K(NT, TNR_MMA_BF16), K(NT, TNR_MMA_BF16X3)
 
 extern "C" int tnr_upconv3_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, const float *wp, tnr_view y, int32_t nf, const float *bias,
                                int32_t act, float slope, int32_t mma, void *stream) {
     Up3FwdK k;
     int64_t tiles;
-    int rc = up3_geometry("upconv3_fwd", N, H, W, nf, &k.tiles_x, &k.tiles_y, &tiles);
+    const int rc = up3_geometry("upconv3_fwd", N, H, W, nf, &k.tiles_x, &k.tiles_y, &tiles);
     if (rc != TNR_OK) return rc;
-    TNR_REQUIRE(wp && up3_view_ok(x, nf) && up3_view_ok(y, nf), "upconv3_fwd: bad views");
-    TNR_REQUIRE(mma == TNR_MMA_F32 || mma == TNR_MMA_BF16 || mma == TNR_MMA_BF16X3, "upconv3_fwd: bad mma %d", mma);
+    TNR_REQUIRE(wp && mp_view_ok(x, nf) && mp_view_ok(y, nf), "upconv3_fwd: bad views");
+    TNR_REQUIRE(mp_mma_ok(mma), "upconv3_fwd: bad mma %d", mma);
     TNR_REQUIRE(act == TNR_ACT_NONE || act == TNR_ACT_LRELU || act == TNR_ACT_RELU, "upconv3_fwd: bad activation %d", act);
     k.x = x.ptr; k.x_ct = x.ctot; k.x_co = x.coff; k.N = N; k.H = H; k.W = W; k.wp = wp;
     k.y = y.ptr; k.y_ct = y.ctot; k.y_co = y.coff;
     k.bias = bias; k.ns = act == TNR_ACT_LRELU ? slope : (act == TNR_ACT_RELU ? 0.f : 1.f);
     static int cus = 0;
 #define U3_FWD(NT, MMA) tnr_kernel_lds(up3_fwd_kernel<NT, MMA>, up3_fwd_lds<NT, MMA>())
-    rc = tnr_kernel_setup(&cus, "upconv3_fwd", {U3_MODES(U3_FWD, 1), U3_MODES(U3_FWD, 2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[6] = {U3_MODES(U3_FWD, 1), U3_MODES(U3_FWD, 2)};
+    return mp_launch(&cus, "upconv3_fwd", {MP_MODES(U3_FWD, 1), MP_MODES(U3_FWD, 2)}, (nf == 64 ? 3 : 0) + mma, dim3((unsigned)tiles), &k, stream);
 #undef U3_FWD
-    const tnr_kernel_lds &kl = table[(nf == 64 ? 3 : 0) + mma];      // (TNR_MMA_F32, _BF16, _BF16X3 = 0, 1, 2)
-    void *args[] = {&k};
-    (void)hipLaunchKernel(kl.fn, dim3((unsigned)tiles), dim3(256), args, kl.lds, (hipStream_t)stream);
-    return tnr_check_launch("upconv3_fwd");
 }
 
 extern "C" int tnr_upconv3_dgrad(tnr_view g, int32_t N, int32_t H, int32_t W, const float *wp, tnr_view gx, int32_t nf, tnr_view mask,
                                  float m_slope, int32_t mma, void *stream) {
     Up3DgradK k;
     int64_t tiles;
-    int rc = up3_geometry("upconv3_dgrad", N, H, W, nf, &k.tiles_x, &k.tiles_y, &tiles);
+    const int rc = up3_geometry("upconv3_dgrad", N, H, W, nf, &k.tiles_x, &k.tiles_y, &tiles);
     if (rc != TNR_OK) return rc;
-    TNR_REQUIRE(wp && up3_view_ok(g, nf) && up3_view_ok(gx, nf) && (mask.ptr == nullptr || up3_view_ok(mask, nf)), "upconv3_dgrad: bad views");
-    TNR_REQUIRE(mma == TNR_MMA_F32 || mma == TNR_MMA_BF16 || mma == TNR_MMA_BF16X3, "upconv3_dgrad: bad mma %d", mma);
+    TNR_REQUIRE(wp && mp_view_ok(g, nf) && mp_view_ok(gx, nf) && (mask.ptr == nullptr || mp_view_ok(mask, nf)), "upconv3_dgrad: bad views");
+    TNR_REQUIRE(mp_mma_ok(mma), "upconv3_dgrad: bad mma %d", mma);
     k.g = g.ptr; k.g_ct = g.ctot; k.g_co = g.coff; k.N = N; k.H = H; k.W = W; k.wp = wp;
     k.gx = gx.ptr; k.gx_ct = gx.ctot; k.gx_co = gx.coff;
     k.m = mask.ptr; k.m_ct = mask.ctot; k.m_co = mask.coff; k.m_slope = m_slope;
     static int cus = 0;
 #define U3_DG(NT, MMA) tnr_kernel_lds(up3_dgrad_kernel<NT, MMA>, up3_dgrad_lds<MMA>())
-    rc = tnr_kernel_setup(&cus, "upconv3_dgrad", {U3_MODES(U3_DG, 1), U3_MODES(U3_DG, 2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[6] = {U3_MODES(U3_DG, 1), U3_MODES(U3_DG, 2)};
+    return mp_launch(&cus, "upconv3_dgrad", {MP_MODES(U3_DG, 1), MP_MODES(U3_DG, 2)}, (nf == 64 ? 3 : 0) + mma, dim3((unsigned)tiles), &k, stream);
 #undef U3_DG
-    const tnr_kernel_lds &kl = table[(nf == 64 ? 3 : 0) + mma];
-    void *args[] = {&k};
-    (void)hipLaunchKernel(kl.fn, dim3((unsigned)tiles), dim3(256), args, kl.lds, (hipStream_t)stream);
-    return tnr_check_launch("upconv3_dgrad");
 }
 
 extern "C" int64_t tnr_upconv3_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t nf) {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
-    const int64_t tiles = (int64_t)tnr_cdiv(W, U3_TW) * tnr_cdiv(H, U3_TH) * N;
-    return (int64_t)up3_wgrad_slabs(tiles) * 25 * nf * nf * (int64_t)sizeof(float);
+    return (int64_t)up3_wgrad_slabs(mp_tiles(N, H, W)) * 25 * nf * nf * (int64_t)sizeof(float);
 }
 
 extern "C" int tnr_upconv3_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H, int32_t W, int32_t nf, float *dw, float alpha, float beta,
@@ -468,25 +381,18 @@ extern "C" int tnr_upconv3_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H, i
     int64_t tiles;
     int rc = up3_geometry("upconv3_wgrad", N, H, W, nf, &k.tiles_x, &k.tiles_y, &tiles);
     if (rc != TNR_OK) return rc;
-    TNR_REQUIRE(dw && ws && up3_view_ok(x, nf) && up3_view_ok(g, nf), "upconv3_wgrad: bad arguments");
+    TNR_REQUIRE(dw && ws && mp_view_ok(x, nf) && mp_view_ok(g, nf), "upconv3_wgrad: bad arguments");
     TNR_REQUIRE(tnr_upconv3_wgrad_workspace_bytes(N, H, W, nf) <= ws_bytes, "upconv3_wgrad: workspace too small");
     k.x = x.ptr; k.x_ct = x.ctot; k.x_co = x.coff; k.N = N; k.H = H; k.W = W;
     k.g = g.ptr; k.g_ct = g.ctot; k.g_co = g.coff;
     k.ws = ws; k.tiles = (int)tiles; k.slabs = up3_wgrad_slabs(tiles);
     static int cus = 0;
 #define U3_WG(NT) tnr_kernel_lds(up3_wgrad_kernel<NT>, up3_wgrad_lds<NT>())
-    rc = tnr_kernel_setup(&cus, "upconv3_wgrad", {U3_WG(1), U3_WG(2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[2] = {U3_WG(1), U3_WG(2)};
+    rc = mp_launch(&cus, "upconv3_wgrad", {U3_WG(1), U3_WG(2)}, nf == 64 ? 1 : 0, dim3(25, (unsigned)k.slabs), &k, stream);
 #undef U3_WG
-    const tnr_kernel_lds &kl = table[nf == 64 ? 1 : 0];
-    void *args[] = {&k};
-    hipStream_t st = (hipStream_t)stream;
-    (void)hipLaunchKernel(kl.fn, dim3(25, (unsigned)k.slabs), dim3(256), args, kl.lds, st);
-    rc = tnr_check_launch("upconv3_wgrad");
     if (rc != TNR_OK) return rc;
     Up3UnfoldK u;
     u.ws = ws; u.slabs = k.slabs; u.nf = nf; u.dw = dw; u.alpha = alpha; u.beta = beta;
-    hipLaunchKernelGGL(up3_wgrad_unfold_kernel, dim3(tnr_cdiv(9 * nf * nf, 256)), dim3(256), 0, st, u);
+    hipLaunchKernelGGL(up3_wgrad_unfold_kernel, dim3(tnr_cdiv(9 * nf * nf, 256)), dim3(256), 0, (hipStream_t)stream, u);
     return tnr_check_launch("upconv3_wgrad_unfold");
 }

@@ -1,6 +1,6 @@
 // The image-to-image decoders' up-conv layer (upsample_mode: upconv -- nearest x2, then a 3x3 pad-1 convolution Cin -> Cout, no activation:
 // a norm layer follows) as the transposed 4x4 stride-2 padding-1 convolution of the LOW-resolution tensor it is, borders included.
-// LR pixel i reaches the HR outputs 2i - 1 + k through folded tap k = 0..3 (common.h tnr_upfold_*); an output of parity a = o mod 2 reads the
+// LR pixel i reaches the HR outputs 2i - 1 + k through folded tap k = 0..3 (common.h tnr_fold_*, 4 taps); an output of parity a = o mod 2 reads the
 // two LR neighbours I - 1 + a + u, u = 0, 1, through folded tap 3 - a - 2u per axis: 4 x 4 = 16 products per LR pixel and channel pair
 // against the 36 of the layer written out in the HR domain.  The up-sampled tensor never exists, in any of the three passes.
 //   forward : y[2I + a, 2J + b] = bias + sum over the parity's 2 x 2 taps of F[ky][kx] x[I + dy, J + dx]        four GEMMs per staged LR tile
@@ -8,9 +8,8 @@
 //   wgrad   : dF[ky][kx][ci][co] = sum over LR pixels x[I + dy, J + dx, ci] g[2I + a, 2J + b, co], then the 16 -> 9 unfold
 // Channel counts are multiples of 4, Cout <= 512, Cin <= 2048 (the decoders run Cin = Cout, 2 Cout and 4 Cout, 32 .. 512 produced channels;
 // the thin layers next to the image run through the same kernels with their rows / reduced channels zero-extended to 32 / 16).
-// Forward and data gradient: a workgroup (4 waves) owns an 8 x 16 LR tile and 32 NT produced channels; wave w owns tile rows 2w, 2w + 1 = one
-// 32-pixel block of the matrix core's B operand (A = the folded weights, so a lane ends up holding 4 consecutive channels of ITS pixel: the
-// store is a float4 per lane).  The activations go through LDS in chunks of the reduced channels (forward: 32 channels of the tile + a
+// Forward and data gradient on mma_pixel.h's tile convention (an 8 x 16 LR tile per workgroup, the lane owns a pixel), a workgroup with 32 NT
+// produced channels.  The activations go through LDS in chunks of the reduced channels (forward: 32 channels of the tile + a
 // one-pixel zero halo, read by all four parities; data gradient: 16 channels of the (2 * 8 + 2) x (2 * 16 + 2) gradient window) in the operand
 // format of the arithmetic -- fp32, bf16, or the exact hi / mid / lo bf16 planes.  The folded weights (16 Cin Cout: up to 33 MB in fp32) never
 // enter LDS: tnr_upconv_i2i_pack lays them out as ready A fragments in consumption order (already split for TNR_MMA_BF16X3, already rounded for
@@ -18,29 +17,23 @@
 // ahead of the matrix core.  Sums: one step per accumulation chain on the matrix core, then VALU fp32 into the chunk's partial sum, then into
 // the running sum (DESIGN.md 29 "Summation").  The tap loops are rolled on purpose: no instance spills (DESIGN.md 29 "Registers").  A wave whose two tile rows lie below the image streams nothing (the 1 x 1 .. 4 x 4 end of the U-Net: the layer is
 // weight-bound there, and the launcher hands out 32-channel row blocks instead of 64 so that twice as many CUs stream disjoint weight slices).
-#include "conv_epilogue.h"
+#include "mma_pixel.h"
 
 namespace {
 
-constexpr int UI_TH = 8, UI_TW = 16;                          // LR pixels per workgroup
-constexpr int UI_FW = UI_TW + 2, UI_FPIX = (UI_TH + 2) * UI_FW;   // forward: the staged tile with its halo, 180 pixels
+constexpr int UI_FW = MP_TW + 2, UI_FPIX = (MP_TH + 2) * UI_FW;   // forward: the staged tile with its halo, 180 pixels
 constexpr int UI_FCK = 32;                                    // forward: reduced channels per LDS fill
 constexpr int UI_FPSF = UI_FCK + 4, UI_FPSB = UI_FCK + 8;     // LDS pixel strides (floats | bf16): an odd number of 16-byte units
-constexpr int UI_GW = 2 * UI_TW + 2, UI_GPIX = (2 * UI_TH + 2) * UI_GW;   // data gradient: the staged window of g, 18 x 34 = 612 pixels
+constexpr int UI_GW = 2 * MP_TW + 2, UI_GPIX = (2 * MP_TH + 2) * UI_GW;   // data gradient: the staged window of g, 18 x 34 = 612 pixels
 constexpr int UI_GPSF = 20, UI_GPSB = 24;                     // 16 channels + pad: 80 | 48 bytes
 constexpr int UI_MAX_COUT = 512, UI_MAX_CIN = 2048;
 
 // floats of one step (a tap x 16 reduced channels) of one 32-row block in the packed image
 __host__ __device__ constexpr int ui_unit(int mma) { return mma == TNR_MMA_F32 ? 512 : (mma == TNR_MMA_BF16 ? 256 : 768); }
 
-template <int NT, int MMA> struct UiFrag {                    // one step's A fragments of a lane: all NT 32-row blocks
-    f32x4 f[MMA == TNR_MMA_F32 ? 2 : 1][NT];
-    tnr_bf16x8 b[MMA == TNR_MMA_BF16X3 ? 3 : 1][NT];
-};
-
 // fragments of step s; `wp` points at the workgroup's first 32-row block: [step][row block][fp32: 8-group][half][row][4] | [plane][half][row][8 bf16]
 template <int NT, int MMA>
-__device__ __forceinline__ void ui_load_w(UiFrag<NT, MMA> &w, const float *wp, const int s, const int R32, const int li, const int half) {
+__device__ __forceinline__ void ui_load_w(MpFrag<NT, MMA> &w, const float *wp, const int s, const int R32, const int li, const int half) {
     constexpr int UNIT = ui_unit(MMA);
     const float *base = wp + (size_t)s * R32 * UNIT;
     if constexpr (MMA == TNR_MMA_F32) {
@@ -49,74 +42,11 @@ __device__ __forceinline__ void ui_load_w(UiFrag<NT, MMA> &w, const float *wp, c
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) w.f[g][nn] = *reinterpret_cast<const f32x4 *>(base + nn * UNIT + ((g * 2 + half) * 32 + li) * 4);
     } else {
-        constexpr int NP = MMA == TNR_MMA_BF16X3 ? 3 : 1;
 #pragma unroll
-        for (int p = 0; p < NP; ++p)
+        for (int p = 0; p < mp_planes(MMA); ++p)
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) w.b[p][nn] = *reinterpret_cast<const tnr_bf16x8 *>(base + nn * UNIT + ((p * 2 + half) * 32 + li) * 4);
     }
-}
-
-// acc += A (this step's weights) x B (16 channels of the lane's pixel, read from LDS at `pf` (fp32) | `pb` + plane * plane_stride (bf16))
-template <int NT, int MMA>
-__device__ __forceinline__ void ui_step(f32x16 (&acc)[NT], const UiFrag<NT, MMA> &w, const float *pf, const __bf16 *pb, const int plane_stride,
-                                        const int half) {
-    if constexpr (MMA == TNR_MMA_F32) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const f32x4 av = *reinterpret_cast<const f32x4 *>(pf + g * 8 + half * 4);
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int nn = 0; nn < NT; ++nn) acc[nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.f[g][nn][m], av[m], acc[nn], 0, 0, 0);
-        }
-    } else {
-        constexpr int NP = MMA == TNR_MMA_BF16X3 ? 3 : 1;
-        tnr_bf16x8 ca[NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) ca[p] = *reinterpret_cast<const tnr_bf16x8 *>(pb + p * plane_stride + half * 8);
-        if constexpr (NP == 3) {
-            // the six kept partial products, smallest first (as in conv_body.h)
-            constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int nn = 0; nn < NT; ++nn) acc[nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.b[TB[q]][nn], ca[TA[q]], acc[nn], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int nn = 0; nn < NT; ++nn) acc[nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.b[0][nn], ca[0], acc[nn], 0, 0, 0);
-        }
-    }
-}
-
-// four channels of a staged pixel into LDS in the operand format: fp32, or NP bf16 planes (exact split; one plane = the rounding)
-template <int MMA>
-__device__ __forceinline__ void ui_stage4(f32x4 v, float *sf, __bf16 *sb, const int plane_stride) {
-    if constexpr (MMA == TNR_MMA_F32) {
-        *reinterpret_cast<f32x4 *>(sf) = v;
-    } else {
-        constexpr int NP = MMA == TNR_MMA_BF16X3 ? 3 : 1;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            tnr_bf16x4 pk;
-            f32x4 res;
-            tnr_pk_level(v, pk, res);
-            *reinterpret_cast<tnr_bf16x4 *>(sb + p * plane_stride) = pk;
-            v = res;
-        }
-    }
-}
-
-template <int NT> __device__ __forceinline__ void ui_zero(f32x16 (&v)[NT]) {
-#pragma unroll
-    for (int nn = 0; nn < NT; ++nn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[nn][r] = 0.f;
-}
-
-template <int NT> __device__ __forceinline__ void ui_add(f32x16 (&acc)[NT], const f32x16 (&part)[NT]) {
-#pragma unroll
-    for (int nn = 0; nn < NT; ++nn) acc[nn] += part[nn];
 }
 
 // ------------------------------------------------------------------------------------------------ weight image
@@ -155,7 +85,7 @@ __global__ void __launch_bounds__(256) ui_pack_kernel(const UiPackK a) {
         const int k = kbase + j;
         const int co = a.dgrad ? k : row, ci = a.dgrad ? row : k;
         float v = 0.f;
-        if (co < a.Cout && ci < a.Cin) v = tnr_upfold_tap(a.w + ((size_t)co * a.Cin + ci) * 9, ky, kx);
+        if (co < a.Cout && ci < a.Cin) v = tnr_fold_tap(a.w + ((size_t)co * a.Cin + ci) * 9, 4, ky, kx);
         if (j < 4) lo[j] = v; else hi[j - 4] = v;
     }
     constexpr int UNIT = ui_unit(MMA);
@@ -165,10 +95,9 @@ __global__ void __launch_bounds__(256) ui_pack_kernel(const UiPackK a) {
         *reinterpret_cast<f32x4 *>(dst + ((k8 * 2 + 0) * 32 + r) * 4) = lo;
         *reinterpret_cast<f32x4 *>(dst + ((k8 * 2 + 1) * 32 + r) * 4) = hi;
     } else {
-        constexpr int NP = MMA == TNR_MMA_BF16X3 ? 3 : 1;
         __bf16 *db = reinterpret_cast<__bf16 *>(dst);
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
+        for (int p = 0; p < mp_planes(MMA); ++p) {
             tnr_bf16x4 pl, ph;
             f32x4 rl, rh;
             tnr_pk_level(lo, pl, rl);
@@ -192,7 +121,7 @@ struct UiFwdK {
 };
 
 template <int MMA> constexpr int ui_fwd_lds() {
-    return MMA == TNR_MMA_F32 ? UI_FPIX * UI_FPSF * 4 : UI_FPIX * UI_FPSB * 2 * (MMA == TNR_MMA_BF16X3 ? 3 : 1);
+    return MMA == TNR_MMA_F32 ? UI_FPIX * UI_FPSF * 4 : UI_FPIX * UI_FPSB * 2 * mp_planes(MMA);
 }
 
 template <int NT, int MMA>
@@ -208,21 +137,21 @@ __global__ void __launch_bounds__(256) ui_fwd_kernel(const UiFwdK a) {
     bid /= a.tiles_x;
     const int ty = bid % a.tiles_y;
     const int n = bid / a.tiles_y;
-    const int y0 = ty * UI_TH, x0 = tx * UI_TW;
+    const int y0 = ty * MP_TH, x0 = tx * MP_TW;
     const int rb0 = blockIdx.y * NT;
     const float *wp = a.wp + (size_t)rb0 * ui_unit(MMA);
     const bool wave_on = y0 + 2 * wave < a.H;                       // wave-uniform: a wave below the image neither streams nor multiplies
     const int chunks = (a.Cin + UI_FCK - 1) / UI_FCK, steps = chunks * 32;
 
-    UiFrag<NT, MMA> cur, nxt;
+    MpFrag<NT, MMA> cur, nxt;
     ui_load_w<NT, MMA>(cur, wp, 0, a.R32, li, half);
     nxt = cur;
 
-    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // this lane's LR pixel (the B operand's column)
-    const int abase = (ly + 1) * UI_FW + lx + 1;
+    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // mma_pixel.h: the lane's pixel of the tile
+    const int abase = (ly + 1) * UI_FW + lx + 1;                    // the lane's LR pixel in the staged tile
     f32x16 acc[4][NT];                                              // the four output parities of the lane's pixel
 #pragma unroll
-    for (int p = 0; p < 4; ++p) ui_zero<NT>(acc[p]);
+    for (int p = 0; p < 4; ++p) mp_zero<NT>(acc[p]);
 
 #pragma unroll 1
     for (int c = 0; c < chunks; ++c) {
@@ -235,14 +164,14 @@ __global__ void __launch_bounds__(256) ui_fwd_kernel(const UiFwdK a) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (Y >= 0 && Y < a.H && X >= 0 && X < a.W && ch < a.Cin)
                 v = *reinterpret_cast<const f32x4 *>(a.x + (((size_t)n * a.H + Y) * a.W + X) * a.x_ct + a.x_co + ch);
-            ui_stage4<MMA>(v, s_f + p * UI_FPSF + c4 * 4, s_b + p * UI_FPSB + c4 * 4, PLANE);
+            mp_stage4<MMA>(v, s_f + p * UI_FPSF + c4 * 4, s_b + p * UI_FPSB + c4 * 4, PLANE);
         }
         __syncthreads();
         if (wave_on) {
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 f32x16 part[NT];                                    // the chunk's 4 taps x 32 channels of this parity, then added to its running sum
-                ui_zero<NT>(part);
+                mp_zero<NT>(part);
                 // the parity's 4 neighbours x 2 half-chunks as a ROLLED loop: unrolled, the scheduler hoists every step's fragment and LDS loads
                 // to the top and the body spills (3 KB of scratch per lane at NT = 2); rolled, one step's operands are live at a time
 #pragma unroll 1
@@ -252,16 +181,16 @@ __global__ void __launch_bounds__(256) ui_fwd_kernel(const UiFwdK a) {
                     const int s = c * 32 + p * 8 + u;
                     if (s + 1 < steps) ui_load_w<NT, MMA>(nxt, wp, s + 1, a.R32, li, half);
                     f32x16 st[NT];                                  // one step = one accumulation chain on the matrix core; the sums above it in VALU fp32
-                    ui_zero<NT>(st);
-                    ui_step<NT, MMA>(st, cur, s_f + pix * UI_FPSF + ks * 16, s_b + pix * UI_FPSB + ks * 16, PLANE, half);
-                    ui_add<NT>(part, st);
+                    mp_zero<NT>(st);
+                    mp_step<NT, MMA>(st, cur, s_f + pix * UI_FPSF + ks * 16, s_b + pix * UI_FPSB + ks * 16, PLANE, half);
+                    mp_add<NT>(part, st);
                     cur = nxt;
                 }
-                ui_add<NT>(acc[p], part);
+                mp_add<NT>(acc[p], part);
             }
         }
     }
-    // ---- pixel (2 (y0 + ly) + a, 2 (x0 + lx) + b) of every parity: the lane holds channels 8 q + 4 half .. + 3 of every 32-block
+    // ---- pixel (2 (y0 + ly) + a, 2 (x0 + lx) + b) of every parity
     if (wave_on && y0 + ly < a.H && x0 + lx < a.W) {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
@@ -292,7 +221,7 @@ struct UiDgradK {
 };
 
 template <int MMA> constexpr int ui_dgrad_lds() {
-    return MMA == TNR_MMA_F32 ? UI_GPIX * UI_GPSF * 4 : UI_GPIX * UI_GPSB * 2 * (MMA == TNR_MMA_BF16X3 ? 3 : 1);
+    return MMA == TNR_MMA_F32 ? UI_GPIX * UI_GPSF * 4 : UI_GPIX * UI_GPSB * 2 * mp_planes(MMA);
 }
 
 template <int NT, int MMA>
@@ -308,21 +237,21 @@ __global__ void __launch_bounds__(256) ui_dgrad_kernel(const UiDgradK a) {
     bid /= a.tiles_x;
     const int ty = bid % a.tiles_y;
     const int n = bid / a.tiles_y;
-    const int y0 = ty * UI_TH, x0 = tx * UI_TW;
+    const int y0 = ty * MP_TH, x0 = tx * MP_TW;
     const int Hh = 2 * a.H, Wh = 2 * a.W;
     const int rb0 = blockIdx.y * NT;
     const float *wp = a.wp + (size_t)rb0 * ui_unit(MMA);
     const bool wave_on = y0 + 2 * wave < a.H;
     const int chunks = (a.Cout + 15) / 16, steps = chunks * 16;
 
-    UiFrag<NT, MMA> cur, nxt;
+    MpFrag<NT, MMA> cur, nxt;
     ui_load_w<NT, MMA>(cur, wp, 0, a.R32, li, half);
     nxt = cur;
 
-    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // this lane's LR pixel; its 4 x 4 window starts at (2 ly, 2 lx)
-    const int abase = 2 * ly * UI_GW + 2 * lx;
+    const int ly = 2 * wave + (li >> 4), lx = li & 15;              // mma_pixel.h: the lane's pixel of the tile
+    const int abase = 2 * ly * UI_GW + 2 * lx;                      // the lane's LR pixel: its 4 x 4 window starts at (2 ly, 2 lx)
     f32x16 acc[NT];
-    ui_zero<NT>(acc);
+    mp_zero<NT>(acc);
 #pragma unroll 1
     for (int c = 0; c < chunks; ++c) {
         if (c) __syncthreads();
@@ -334,23 +263,23 @@ __global__ void __launch_bounds__(256) ui_dgrad_kernel(const UiDgradK a) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (Y >= 0 && Y < Hh && X >= 0 && X < Wh && ch < a.Cout)
                 v = *reinterpret_cast<const f32x4 *>(a.g + (((size_t)n * Hh + Y) * Wh + X) * a.g_ct + a.g_co + ch);
-            ui_stage4<MMA>(v, s_f + p * UI_GPSF + c4 * 4, s_b + p * UI_GPSB + c4 * 4, PLANE);
+            mp_stage4<MMA>(v, s_f + p * UI_GPSF + c4 * 4, s_b + p * UI_GPSB + c4 * 4, PLANE);
         }
         __syncthreads();
         if (wave_on) {
             f32x16 part[NT];                                        // the chunk's 16 taps x 16 channels, then added to the running sum
-            ui_zero<NT>(part);
+            mp_zero<NT>(part);
 #pragma unroll 1
             for (int t = 0; t < 16; ++t) {                          // (rolled for the same reason as the forward's tap loop)
                 const int s = c * 16 + t, pix = abase + (t >> 2) * UI_GW + (t & 3);
                 if (s + 1 < steps) ui_load_w<NT, MMA>(nxt, wp, s + 1, a.R32, li, half);
                 f32x16 st[NT];                                      // (as in the forward: one step per matrix-core accumulation chain)
-                ui_zero<NT>(st);
-                ui_step<NT, MMA>(st, cur, s_f + pix * UI_GPSF, s_b + pix * UI_GPSB, PLANE, half);
-                ui_add<NT>(part, st);
+                mp_zero<NT>(st);
+                mp_step<NT, MMA>(st, cur, s_f + pix * UI_GPSF, s_b + pix * UI_GPSB, PLANE, half);
+                mp_add<NT>(part, st);
                 cur = nxt;
             }
-            ui_add<NT>(acc, part);
+            mp_add<NT>(acc, part);
         }
     }
     if (wave_on && y0 + ly < a.H && x0 + lx < a.W) {
@@ -376,7 +305,7 @@ struct UiWgradK {
 };
 
 template <int NI, int NO> constexpr int ui_wgrad_lds() {
-    constexpr int stage = UI_TH * UI_TW * (NI + NO) * 32 * 4, reduce = 4 * NI * 32 * NO * 32 * 4;
+    constexpr int stage = MP_TPIX * (NI + NO) * 32 * 4, reduce = 4 * NI * 32 * NO * 32 * 4;
     return stage > reduce ? stage : reduce;
 }
 
@@ -387,7 +316,7 @@ template <int NI, int NO> constexpr int ui_wgrad_lds() {
 // waves' sums are then added in wave order through LDS: the order in which every partial sum grows is fixed.
 template <int NI, int NO>
 __global__ void __launch_bounds__(256) ui_wgrad_kernel(const UiWgradK a) {
-    constexpr int CI = NI * 32, CO = NO * 32, TPIX = UI_TH * UI_TW;
+    constexpr int CI = NI * 32, CO = NO * 32, TPIX = MP_TPIX;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *s_x = reinterpret_cast<float *>(smem);
     float *s_g = s_x + TPIX * CI;
@@ -405,7 +334,7 @@ __global__ void __launch_bounds__(256) ui_wgrad_kernel(const UiWgradK a) {
 
     f32x16 acc[NI][NO];
 #pragma unroll
-    for (int ib = 0; ib < NI; ++ib) ui_zero<NO>(acc[ib]);
+    for (int ib = 0; ib < NI; ++ib) mp_zero<NO>(acc[ib]);
 
     for (int tile = blockIdx.y; tile < a.tiles; tile += a.slabs) {
         int q = tile;
@@ -413,11 +342,11 @@ __global__ void __launch_bounds__(256) ui_wgrad_kernel(const UiWgradK a) {
         q /= a.tiles_x;
         const int ty = q % a.tiles_y;
         const int n = q / a.tiles_y;
-        const int y0 = ty * UI_TH, x0 = tx * UI_TW;
+        const int y0 = ty * MP_TH, x0 = tx * MP_TW;
         __syncthreads();
         for (int i = tid; i < TPIX * (CI / 4); i += 256) {
             const int p = i / (CI / 4), c4 = i - p * (CI / 4);
-            const int I = y0 + p / UI_TW, J = x0 + p % UI_TW, Y = I + dy, X = J + dx, ch = ci0 + c4 * 4;
+            const int I = y0 + p / MP_TW, J = x0 + p % MP_TW, Y = I + dy, X = J + dx, ch = ci0 + c4 * 4;
             f32x4 xv = {0.f, 0.f, 0.f, 0.f};
             if (I < a.H && J < a.W && Y >= 0 && Y < a.H && X >= 0 && X < a.W && ch < a.Cin)
                 xv = *reinterpret_cast<const f32x4 *>(a.x + (((size_t)n * a.H + Y) * a.W + X) * a.x_ct + a.x_co + ch);
@@ -425,7 +354,7 @@ __global__ void __launch_bounds__(256) ui_wgrad_kernel(const UiWgradK a) {
         }
         for (int i = tid; i < TPIX * (CO / 4); i += 256) {
             const int p = i / (CO / 4), c4 = i - p * (CO / 4);
-            const int I = y0 + p / UI_TW, J = x0 + p % UI_TW, ch = co0 + c4 * 4;
+            const int I = y0 + p / MP_TW, J = x0 + p % MP_TW, ch = co0 + c4 * 4;
             f32x4 gv = {0.f, 0.f, 0.f, 0.f};
             if (I < a.H && J < a.W && ch < a.Cout)
                 gv = *reinterpret_cast<const f32x4 *>(a.g + (((size_t)n * Hh + 2 * I + pa) * Wh + 2 * J + pb) * a.g_ct + a.g_co + ch);
@@ -497,19 +426,13 @@ bool ui_channels_ok(int Cin, int Cout) {
 }
 
 int ui_geometry(const char *who, int N, int H, int W, int Cin, int Cout, int *tiles_x, int *tiles_y, int64_t *tiles) {
-    TNR_REQUIRE(N > 0 && H > 0 && W > 0, "%s: bad arguments", who);
+    const int rc = mp_geometry(who, N, H, W, 2, tiles_x, tiles_y, tiles);
+    if (rc != TNR_OK) return rc;
     TNR_REQUIRE(ui_channels_ok(Cin, Cout),
                 "%s: built for 4 <= Cout <= %d and 4 <= Cin <= %d, both multiples of 4 (got %d -> %d)", who, UI_MAX_COUT, UI_MAX_CIN, Cin, Cout);
-    TNR_REQUIRE((int64_t)2 * H < (1 << 30) && (int64_t)2 * W < (1 << 30), "%s: image too large", who);
-    *tiles_x = tnr_cdiv(W, UI_TW);
-    *tiles_y = tnr_cdiv(H, UI_TH);
-    *tiles = (int64_t)*tiles_x * *tiles_y * N;
-    TNR_REQUIRE(*tiles < (1LL << 31), "%s: grid too large", who);
     return TNR_OK;
 }
 
-bool ui_view_ok(const tnr_view &v, int C) { return v.ptr != nullptr && view_aligned(v) && v.coff >= 0 && v.coff + C <= v.ctot; }
-bool ui_mma_ok(int mma) { return mma == TNR_MMA_F32 || mma == TNR_MMA_BF16 || mma == TNR_MMA_BF16X3; }
 int ui_steps(int Cout, int Cin, int dgrad) { return dgrad ? tnr_cdiv(Cout, 16) * 16 : tnr_cdiv(Cin, UI_FCK) * 32; }
 int ui_rows32(int Cout, int Cin, int dgrad) { return tnr_cdiv(dgrad ? Cin : Cout, 32); }
 
@@ -529,10 +452,8 @@ int ui_wgrad_slabs(int64_t tiles, int Cin, int Cout) {
 
 }  // namespace
 
-#define UI_MODES(K, NT) K(NT, TNR_MMA_F32), K(NT, TNR_MMA_BF16), K(NT, TNR_MMA_BF16X3)
-
 extern "C" int64_t tnr_upconv_i2i_pack_floats(int32_t Cout, int32_t Cin, int32_t dgrad, int32_t mma) {
-    if (!ui_channels_ok(Cin, Cout) || !ui_mma_ok(mma)) return 0;
+    if (!ui_channels_ok(Cin, Cout) || !mp_mma_ok(mma)) return 0;
     return (int64_t)ui_steps(Cout, Cin, dgrad) * ui_rows32(Cout, Cin, dgrad) * ui_unit(mma);
 }
 
@@ -541,7 +462,7 @@ extern "C" int tnr_upconv_i2i_pack(const float *w, int32_t Cout, int32_t Cin, in
     TNR_REQUIRE(w && out && (reinterpret_cast<uintptr_t>(out) & 15) == 0, "upconv_i2i_pack: bad pointers");
     TNR_REQUIRE(ui_channels_ok(Cin, Cout),
                 "upconv_i2i_pack: built for 4 <= Cout <= %d and 4 <= Cin <= %d, both multiples of 4 (got %d -> %d)", UI_MAX_COUT, UI_MAX_CIN, Cin, Cout);
-    TNR_REQUIRE(ui_mma_ok(mma), "upconv_i2i_pack: bad mma %d", mma);
+    TNR_REQUIRE(mp_mma_ok(mma), "upconv_i2i_pack: bad mma %d", mma);
     TNR_REQUIRE(tnr_upconv_i2i_pack_floats(Cout, Cin, dgrad, mma) <= out_floats, "upconv_i2i_pack: image buffer too small");
     UiPackK k;
     k.w = w; k.out = out; k.Cout = Cout; k.Cin = Cin; k.dgrad = dgrad != 0; k.R32 = ui_rows32(Cout, Cin, dgrad);
@@ -560,22 +481,19 @@ extern "C" int tnr_upconv_i2i_fwd(tnr_view x, int32_t N, int32_t H, int32_t W, i
     int64_t tiles;
     int rc = ui_geometry("upconv_i2i_fwd", N, H, W, Cin, Cout, &k.tiles_x, &k.tiles_y, &tiles);
     if (rc != TNR_OK) return rc;
-    TNR_REQUIRE(wp && ui_view_ok(x, Cin) && ui_view_ok(y, Cout), "upconv_i2i_fwd: bad views");
-    TNR_REQUIRE(ui_mma_ok(mma), "upconv_i2i_fwd: bad mma %d", mma);
+    TNR_REQUIRE(wp && mp_view_ok(x, Cin) && mp_view_ok(y, Cout), "upconv_i2i_fwd: bad views");
+    TNR_REQUIRE(mp_mma_ok(mma), "upconv_i2i_fwd: bad mma %d", mma);
     k.x = x.ptr; k.x_ct = x.ctot; k.x_co = x.coff; k.N = N; k.H = H; k.W = W; k.Cin = Cin;
     k.wp = wp; k.R32 = ui_rows32(Cout, Cin, 0);
     k.y = y.ptr; k.y_ct = y.ctot; k.y_co = y.coff; k.Cout = Cout; k.bias = bias;
     static int cus = 0;
 #define UI_FWD(NT, MMA) tnr_kernel_lds(ui_fwd_kernel<NT, MMA>, ui_fwd_lds<MMA>())
-    rc = tnr_kernel_setup(&cus, "upconv_i2i_fwd", {UI_MODES(UI_FWD, 1), UI_MODES(UI_FWD, 2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[6] = {UI_MODES(UI_FWD, 1), UI_MODES(UI_FWD, 2)};
+    const std::initializer_list<tnr_kernel_lds> table = {MP_MODES(UI_FWD, 1), MP_MODES(UI_FWD, 2)};
 #undef UI_FWD
+    rc = tnr_kernel_setup(&cus, "upconv_i2i_fwd", table);           // (the row-block choice reads the CU count)
+    if (rc != TNR_OK) return rc;
     const int nt = ui_row_blocks(k.R32, tiles, cus);
-    const tnr_kernel_lds &kl = table[(nt == 2 ? 3 : 0) + mma];       // (TNR_MMA_F32, _BF16, _BF16X3 = 0, 1, 2)
-    void *args[] = {&k};
-    (void)hipLaunchKernel(kl.fn, dim3((unsigned)tiles, (unsigned)(k.R32 / nt)), dim3(256), args, kl.lds, (hipStream_t)stream);
-    return tnr_check_launch("upconv_i2i_fwd");
+    return mp_launch_entry("upconv_i2i_fwd", table, (nt == 2 ? 3 : 0) + mma, dim3((unsigned)tiles, (unsigned)(k.R32 / nt)), &k, stream);
 }
 
 extern "C" int tnr_upconv_i2i_dgrad(tnr_view g, int32_t N, int32_t H, int32_t W, int32_t Cout, const float *wp, tnr_view gx, int32_t Cin,
@@ -584,28 +502,24 @@ extern "C" int tnr_upconv_i2i_dgrad(tnr_view g, int32_t N, int32_t H, int32_t W,
     int64_t tiles;
     int rc = ui_geometry("upconv_i2i_dgrad", N, H, W, Cin, Cout, &k.tiles_x, &k.tiles_y, &tiles);
     if (rc != TNR_OK) return rc;
-    TNR_REQUIRE(wp && ui_view_ok(g, Cout) && ui_view_ok(gx, Cin), "upconv_i2i_dgrad: bad views");
-    TNR_REQUIRE(ui_mma_ok(mma), "upconv_i2i_dgrad: bad mma %d", mma);
+    TNR_REQUIRE(wp && mp_view_ok(g, Cout) && mp_view_ok(gx, Cin), "upconv_i2i_dgrad: bad views");
+    TNR_REQUIRE(mp_mma_ok(mma), "upconv_i2i_dgrad: bad mma %d", mma);
     k.g = g.ptr; k.g_ct = g.ctot; k.g_co = g.coff; k.N = N; k.H = H; k.W = W; k.Cout = Cout;
     k.wp = wp; k.R32 = ui_rows32(Cout, Cin, 1);
     k.gx = gx.ptr; k.gx_ct = gx.ctot; k.gx_co = gx.coff; k.Cin = Cin;
     static int cus = 0;
 #define UI_DG(NT, MMA) tnr_kernel_lds(ui_dgrad_kernel<NT, MMA>, ui_dgrad_lds<MMA>())
-    rc = tnr_kernel_setup(&cus, "upconv_i2i_dgrad", {UI_MODES(UI_DG, 1), UI_MODES(UI_DG, 2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[6] = {UI_MODES(UI_DG, 1), UI_MODES(UI_DG, 2)};
+    const std::initializer_list<tnr_kernel_lds> table = {MP_MODES(UI_DG, 1), MP_MODES(UI_DG, 2)};
 #undef UI_DG
+    rc = tnr_kernel_setup(&cus, "upconv_i2i_dgrad", table);
+    if (rc != TNR_OK) return rc;
     const int nt = ui_row_blocks(k.R32, tiles, cus);
-    const tnr_kernel_lds &kl = table[(nt == 2 ? 3 : 0) + mma];
-    void *args[] = {&k};
-    (void)hipLaunchKernel(kl.fn, dim3((unsigned)tiles, (unsigned)(k.R32 / nt)), dim3(256), args, kl.lds, (hipStream_t)stream);
-    return tnr_check_launch("upconv_i2i_dgrad");
+    return mp_launch_entry("upconv_i2i_dgrad", table, (nt == 2 ? 3 : 0) + mma, dim3((unsigned)tiles, (unsigned)(k.R32 / nt)), &k, stream);
 }
 
 extern "C" int64_t tnr_upconv_i2i_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout) {
     if (N <= 0 || H <= 0 || W <= 0 || !ui_channels_ok(Cin, Cout)) return 0;
-    const int64_t tiles = (int64_t)tnr_cdiv(W, UI_TW) * tnr_cdiv(H, UI_TH) * N;
-    return (int64_t)ui_wgrad_slabs(tiles, Cin, Cout) * 16 * tnr_round_up(Cin, 32) * tnr_round_up(Cout, 32) * (int64_t)sizeof(float);
+    return (int64_t)ui_wgrad_slabs(mp_tiles(N, H, W), Cin, Cout) * 16 * tnr_round_up(Cin, 32) * tnr_round_up(Cout, 32) * (int64_t)sizeof(float);
 }
 
 extern "C" int tnr_upconv_i2i_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, float *dw, float alpha,
@@ -614,7 +528,7 @@ extern "C" int tnr_upconv_i2i_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H
     int64_t tiles;
     int rc = ui_geometry("upconv_i2i_wgrad", N, H, W, Cin, Cout, &k.tiles_x, &k.tiles_y, &tiles);
     if (rc != TNR_OK) return rc;
-    TNR_REQUIRE(dw && ws && ui_view_ok(x, Cin) && ui_view_ok(g, Cout), "upconv_i2i_wgrad: bad arguments");
+    TNR_REQUIRE(dw && ws && mp_view_ok(x, Cin) && mp_view_ok(g, Cout), "upconv_i2i_wgrad: bad arguments");
     TNR_REQUIRE(tnr_upconv_i2i_wgrad_workspace_bytes(N, H, W, Cin, Cout) <= ws_bytes, "upconv_i2i_wgrad: workspace too small");
     k.x = x.ptr; k.x_ct = x.ctot; k.x_co = x.coff; k.N = N; k.H = H; k.W = W; k.Cin = Cin;
     k.g = g.ptr; k.g_ct = g.ctot; k.g_co = g.coff; k.Cout = Cout;
@@ -624,18 +538,12 @@ extern "C" int tnr_upconv_i2i_wgrad(tnr_view x, tnr_view g, int32_t N, int32_t H
     k.tiles = (int)tiles; k.slabs = ui_wgrad_slabs(tiles, Cin, Cout);
     static int cus = 0;
 #define UI_WG(NI, NO) tnr_kernel_lds(ui_wgrad_kernel<NI, NO>, ui_wgrad_lds<NI, NO>())
-    rc = tnr_kernel_setup(&cus, "upconv_i2i_wgrad", {UI_WG(1, 1), UI_WG(1, 2), UI_WG(2, 1), UI_WG(2, 2)});
-    if (rc != TNR_OK) return rc;
-    const tnr_kernel_lds table[4] = {UI_WG(1, 1), UI_WG(1, 2), UI_WG(2, 1), UI_WG(2, 2)};
+    rc = mp_launch(&cus, "upconv_i2i_wgrad", {UI_WG(1, 1), UI_WG(1, 2), UI_WG(2, 1), UI_WG(2, 2)}, (ni - 1) * 2 + (no - 1),
+                   dim3((unsigned)(16 * k.nbi * k.nbo), (unsigned)k.slabs), &k, stream);
 #undef UI_WG
-    const tnr_kernel_lds &kl = table[(ni - 1) * 2 + (no - 1)];
-    void *args[] = {&k};
-    hipStream_t st = (hipStream_t)stream;
-    (void)hipLaunchKernel(kl.fn, dim3((unsigned)(16 * k.nbi * k.nbo), (unsigned)k.slabs), dim3(256), args, kl.lds, st);
-    rc = tnr_check_launch("upconv_i2i_wgrad");
     if (rc != TNR_OK) return rc;
     UiUnfoldK u;
     u.ws = ws; u.slabs = k.slabs; u.Cin = Cin; u.Cout = Cout; u.CinP = k.CinP; u.CoutP = k.CoutP; u.dw = dw; u.alpha = alpha; u.beta = beta;
-    hipLaunchKernelGGL(ui_wgrad_unfold_kernel, dim3(tnr_cdiv(9 * Cin * Cout, 256)), dim3(256), 0, st, u);
+    hipLaunchKernelGGL(ui_wgrad_unfold_kernel, dim3(tnr_cdiv(9 * Cin * Cout, 256)), dim3(256), 0, (hipStream_t)stream, u);
     return tnr_check_launch("upconv_i2i_wgrad_unfold");
 }

@@ -168,7 +168,7 @@ __global__ void pack_weights_kernel(const tnr_pack_item *items) {
             const int par = (int)(q >> 2);
             const int py = par >> 1, px = par & 1;
             const int ky = ((py + 1) & 1) + 2 * (t >> 1), kx = ((px + 1) & 1) + 2 * (t & 1);
-            if (co < Cout && ci < Cin) v = tnr_upfold_tap(it.w + ((size_t)co * Cin + ci) * 9, ky, kx);
+            if (co < Cout && ci < Cin) v = tnr_fold_tap(it.w + ((size_t)co * Cin + ci) * 9, 4, ky, kx);
         } else if (it.kind == TNR_PACK_UP2_FWD_S2D) {    // TNR_PACK_FWD_S2D's layout of the folded S: [t][ci][pp][co]
             const int vch = (int)(e % (4 * ki));
             int64_t q = e / (4 * ki);
@@ -176,7 +176,7 @@ __global__ void pack_weights_kernel(const tnr_pack_item *items) {
             const int t = (int)(q / ko);
             const int pp = vch / ki, co = vch - pp * ki;   // reduction channel = the 3x3 layer's output
             const int ky = 2 * (t >> 1) + (pp >> 1), kx = 2 * (t & 1) + (pp & 1);
-            if (co < Cout && ci < Cin) v = tnr_upfold_tap(it.w + ((size_t)co * Cin + ci) * 9, ky, kx);
+            if (co < Cout && ci < Cin) v = tnr_fold_tap(it.w + ((size_t)co * Cin + ci) * 9, 4, ky, kx);
         } else if (it.kind == TNR_PACK_UP3_FWD || it.kind == TNR_PACK_UP3_DGRAD) {
             // step s = one folded tap x 16 reduced channels.  fp32 region: [s][8-group][lane half][row][4]; bf16 region behind it:
             // [s][plane][lane half][row][8 bf16] -- a lane's A fragment of v_mfma_f32_32x32x2_f32 (x4) | v_mfma_f32_32x32x16_bf16 is 16 bytes
@@ -217,7 +217,7 @@ __global__ void pack_weights_kernel(const tnr_pack_item *items) {
             }
             auto tap = [&](int c) {                   // row = produced channel, c = reduced channel
                 const int co = fwd ? row : c, ci = fwd ? c : row;
-                return tnr_up3fold_tap(it.w + ((size_t)co * Cin + ci) * 9, ky, kx);
+                return tnr_fold_tap(it.w + ((size_t)co * Cin + ci) * 9, 5, ky, kx);
             };
             if (plane < 0) {
                 v = tap(ks * 16 + c0);
@@ -300,25 +300,18 @@ extern "C" int tnr_pack_dense_dgrad(const tnr_dense_pack_item *items_dev, int32_
     return tnr_check_launch("pack_dense_dgrad");
 }
 
-extern "C" int tnr_upconv_fold_table(int32_t out[144]) {
-    TNR_REQUIRE(out != nullptr, "upconv_fold_table: null pointer");
-    for (int k = 0; k < 16; ++k)
+// out[(ky * T + kx) * 9 + ty * 3 + tx] = 1 where folded tap (ky, kx) of T per axis sums 3x3 tap (ty, tx), from the helpers the packs fold with
+static int fold_table(const char *who, int T, int32_t *out) {
+    TNR_REQUIRE(out != nullptr, "%s: null pointer", who);
+    for (int k = 0; k < T * T; ++k)
         for (int t = 0; t < 9; ++t) {
-            const int ky = k >> 2, kx = k & 3, ty = t / 3, tx = t % 3;
-            out[k * 9 + t] = ty >= tnr_upfold_lo(ky) && ty <= tnr_upfold_hi(ky) && tx >= tnr_upfold_lo(kx) && tx <= tnr_upfold_hi(kx);
+            const int ky = k / T, kx = k % T, ty = t / 3, tx = t % 3;
+            out[k * 9 + t] = ty >= tnr_fold_lo(ky) && ty <= tnr_fold_hi(T, ky) && tx >= tnr_fold_lo(kx) && tx <= tnr_fold_hi(T, kx);
         }
     return TNR_OK;
 }
-
-extern "C" int tnr_upconv3_fold_table(int32_t out[225]) {
-    TNR_REQUIRE(out != nullptr, "upconv3_fold_table: null pointer");
-    for (int k = 0; k < 25; ++k)
-        for (int t = 0; t < 9; ++t) {
-            const int ky = k / 5, kx = k % 5, ty = t / 3, tx = t % 3;
-            out[k * 9 + t] = ty >= tnr_up3fold_lo(ky) && ty <= tnr_up3fold_hi(ky) && tx >= tnr_up3fold_lo(kx) && tx <= tnr_up3fold_hi(kx);
-        }
-    return TNR_OK;
-}
+extern "C" int tnr_upconv_fold_table(int32_t out[144]) { return fold_table("upconv_fold_table", 4, out); }
+extern "C" int tnr_upconv3_fold_table(int32_t out[225]) { return fold_table("upconv3_fold_table", 5, out); }
 
 extern "C" int tnr_pack_weights(const tnr_pack_item *items_dev, int32_t n, int64_t max_out, void *stream) {
     TNR_REQUIRE(items_dev != nullptr && n > 0 && max_out > 0, "pack: bad arguments");

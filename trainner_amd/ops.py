@@ -738,7 +738,7 @@ def conv_pool2(x, wp, y, route=None, layer=None, wino=None, **epi):
 # ----------------------------------------------------------------------------------------------
 UPFOLD_FAMILY = "conv_upfold"           # PROFILE family of the folded launches (all three passes), counted with the FLOP they execute (16 taps)
 UPFOLD_PASSES = ("fwd", "dgrad", "wgrad")
-# per axis: the 3x3 taps summed into folded tap k = 0..3 (csrc/common.h tnr_upfold_lo / tnr_upfold_hi)
+# per axis: the 3x3 taps summed into folded tap k = 0..3 (csrc/common.h tnr_fold_lo / tnr_fold_hi at T = 4)
 UPFOLD_TAPS = ((2,), (1, 2), (0, 1), (0,))
 # The passes TNR_UPCONV_FOLD=1 folds (upconv_plan): both gradients, NOT the forward.  The folded forward is the more accurate form against
 # fp64 and 1.1 ms / step faster, but it moves the SR batch itself (1.7e-6 of its scale in the first step), and the GAN step amplifies a
@@ -790,7 +790,7 @@ def upconv_fold_table():
 
 
 def upconv_fold_weights(w):
-    """[..., 3, 3] -> the folded [..., 4, 4] taps in the library's fp32 order (tnr_upfold_tap): inside a row over ascending kx first,
+    """[..., 3, 3] -> the folded [..., 4, 4] taps in the library's fp32 order (tnr_fold_tap): inside a row over ascending kx first,
     then the row sums over ascending ky.  The channel swap of S is the packings' business, not this function's."""
     rows = []
     for ty in range(3):      # row sums: [..., 4] per 3x3 row
@@ -817,7 +817,7 @@ def upconv_wgrad_unfold(dws, dw3, alpha=1.0, beta=1.0):
 # nearest x3 + 3x3 (RRDBNet upscale 3) as the transposed 5x5 stride-3 padding-1 convolution of the LR tensor (csrc/conv_up3.hip)
 # ----------------------------------------------------------------------------------------------
 UP3_FAMILY = "conv_up3"                 # PROFILE family of the three launches, counted with the FLOP they execute (25 taps per LR pixel)
-# per axis: the 3x3 taps summed into folded tap k = 0..4 (csrc/common.h tnr_up3fold_lo / tnr_up3fold_hi); LR pixel i reaches output 3i - 1 + k
+# per axis: the 3x3 taps summed into folded tap k = 0..4 (csrc/common.h tnr_fold_lo / tnr_fold_hi at T = 5); LR pixel i reaches output 3i - 1 + k
 UP3FOLD_TAPS = ((2,), (1, 2), (0, 1, 2), (0, 1), (0,))
 
 
@@ -836,7 +836,7 @@ def _sum_asc(terms):
 
 
 def upconv3_fold_weights(w):
-    """[..., 3, 3] -> the folded [..., 5, 5] taps in the library's order (tnr_up3fold_tap): inside a row over ascending kx first, then
+    """[..., 3, 3] -> the folded [..., 5, 5] taps in the library's order (tnr_fold_tap): inside a row over ascending kx first, then
     the row sums over ascending ky.  F.conv_transpose2d(x, fold(w).transpose(0, 1), stride=3, padding=1) IS the layer."""
     rows = [torch.stack([_sum_asc([w[..., ty, tx] for tx in t]) for t in UP3FOLD_TAPS], dim=-1) for ty in range(3)]
     return torch.stack([_sum_asc([rows[ty] for ty in t]) for t in UP3FOLD_TAPS], dim=-2)
